@@ -7,6 +7,10 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+# The multi-rank launches below are the CPU/gloo shape of the driver's N-GPU
+# run: their ranks must not claim GPUs (a 1-GPU machine has no cuda:1).
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
+
 
 def run_bench(*args):
     env = dict(os.environ, PYTHONPATH=REPO)
@@ -34,6 +38,34 @@ def test_bench_json_contract():
     assert out["value"] > 0
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float32 .npy;
+    weights and inputs are seeded, so a second run reproduces them. --full is
+    accepted and keeps the one-line contract."""
+    import numpy as np
+
+    runs = []
+    for name, extra in (("a", ()), ("b", ("--full",))):
+        d = tmp_path / name
+        out = run_bench("--model", "resnet50", "--dump-outputs", str(d), *extra)
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert sorted(p.name for p in d.iterdir()) == ["logits.npy", "loss.npy", "params.npy"]
+        arrs = {p.stem: np.load(p) for p in d.iterdir()}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 1024 * 1024
+        assert arrs["logits"].shape == (out["config"]["global_batch"], 1000)
+        assert arrs["params"].ndim == 1 and arrs["params"].size > 0
+        assert arrs["loss"].shape == ()
+        assert abs(float(arrs["loss"]) - out["config"]["loss"]) < 1e-6
+        assert all(np.isfinite(a).all() for a in arrs.values())
+        runs.append(arrs)
+    # Same seeds, same kernels: only the order of fp32 reductions may differ
+    # between runs (~1e-6 relative over these 3 steps), far below what
+    # unseeded weights or inputs would give (O(1)).
+    for k in runs[0]:
+        assert np.allclose(runs[0][k], runs[1][k], rtol=1e-3, atol=1e-4), k
+
+
 def test_bench_torch_impl_ab_path():
     out = run_bench("--impl", "torch", "--model", "resnet50")
     assert out["config"]["impl"] == "torch"
@@ -43,7 +75,7 @@ def test_bench_torch_impl_ab_path():
 def test_bench_under_torchrun_two_ranks():
     """The driver's exact N>1 launch shape: torchrun, one JSON from rank 0,
     whole-job aggregate value, allreduce over gloo."""
-    env = dict(os.environ, PYTHONPATH=REPO)
+    env = dict(os.environ, PYTHONPATH=REPO, **NO_GPU)
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
@@ -62,7 +94,7 @@ def test_bench_under_torchrun_eight_ranks():
     """the 8-rank shape of the driver's scaling run,
     exercised on CPU/gloo so the first 8-GPU execution is not the first
     8-rank execution of the bucket-overlap + MAX-over-ranks path."""
-    env = dict(os.environ, PYTHONPATH=REPO)
+    env = dict(os.environ, PYTHONPATH=REPO, **NO_GPU)
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "8", "--master-addr", "127.0.0.1",

@@ -16,6 +16,10 @@ def _dist_env(rank, world, port):
     os.environ["LOCAL_RANK"] = str(rank)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
+    # CPU/gloo ranks: they must not claim GPUs (a 1-GPU machine has no cuda:1
+    # for rank 1). Set before anything initialises the HIP runtime.
+    os.environ["HIP_VISIBLE_DEVICES"] = "-1"
+    os.environ["CUDA_VISIBLE_DEVICES"] = "-1"
 
 
 def _worker_allreduce(rank, world, port, q):

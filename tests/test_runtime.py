@@ -15,7 +15,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def run_amdrun(args, timeout=120):
-    env = dict(os.environ, PYTHONPATH=REPO)
+    # local CPU/gloo ranks: they must not claim GPUs (a 1-GPU machine has no
+    # cuda:1 for local rank 1)
+    env = dict(os.environ, PYTHONPATH=REPO,
+               HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     return subprocess.run([sys.executable, "-m", "mpi_operator_amd.runtime.launcher",
                            *args], capture_output=True, text=True, timeout=timeout,
                           env=env, cwd=REPO)
@@ -32,8 +35,8 @@ def test_hostfile_formats():
 @pytest.mark.timeout(120)
 def test_amdrun_local_ranks_env():
     code = ("import os,sys; "
-            "print('R', os.environ['RANK'], os.environ['LOCAL_RANK'], "
-            "os.environ['WORLD_SIZE'], os.environ['OMPI_COMM_WORLD_RANK'])")
+            "sys.stdout.write(' '.join(['R', os.environ['RANK'], os.environ['LOCAL_RANK'], "
+            "os.environ['WORLD_SIZE'], os.environ['OMPI_COMM_WORLD_RANK']]) + '\\n')")
     r = run_amdrun(["-np", "3", "--", sys.executable, "-c", code])
     assert r.returncode == 0, r.stderr
     lines = sorted(l for l in r.stdout.splitlines() if l.startswith("R "))
@@ -52,13 +55,16 @@ def test_amdrun_gloo_allreduce():
     """End-to-end: amdrun boots 2 ranks that rendezvous through our parallel
     layer (gloo here; identical code path is RCCL on MI355X)."""
     code = textwrap.dedent("""
+        import sys
         import torch
         from mpi_operator_amd import parallel as hvd
         hvd.init(backend="gloo")
         t = torch.full((4,), float(hvd.rank()))
         hvd.allreduce_(t)
         assert t.tolist() == [0.5]*4, t
-        print("OK", hvd.rank(), hvd.size())
+        # one write per line: ranks share the pipe, and print() with several
+        # arguments can interleave with the other rank when unbuffered
+        sys.stdout.write("OK %d %d\\n" % (hvd.rank(), hvd.size()))
         hvd.shutdown()
     """)
     r = run_amdrun(["-np", "2", "--master-port", "29613", "--",
