@@ -112,6 +112,171 @@ __global__ void bn_partials_k(const ushort8 *__restrict__ x,
   }
 }
 
+// Accumulation steps and the block tail of bn_partials_k above, restated for
+// the split-K reduce+stats kernels below: same row assignment, same order,
+// same roundings, so a statistic computed there is bit-identical to the one
+// bn_partials_k computes from the same (rounded) tensor
+// (tests/test_conv_bn_fused_gpu.py asserts equality). bn_partials_k keeps its
+// own text so its code, and with it every unfused result, stays as it was.
+DEV_INLINE void bn_acc_fwd(float *a0, float *a1, const float *fx,
+                           const float *fx2) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    a0[j] += fx[j] + fx2[j];
+    a1[j] += fx[j] * fx[j] + fx2[j] * fx2[j];
+  }
+}
+
+// fdy/fdy2 are gated in place by the ReLU mask (bitmask if given, else y>0)
+DEV_INLINE void bn_acc_bwd(float *a0, float *a1, const float *fx,
+                           const float *fx2, float *fdy, float *fdy2,
+                           const ushort8 *__restrict__ y,
+                           const uint8_t *__restrict__ mask, long off,
+                           long off2, bool has2, int relu, const float *mn,
+                           const float *is) {
+  if (relu) {
+    if (mask) {
+      int m1 = mask[off], m2 = has2 ? mask[off2] : 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (!(m1 & (1 << j))) fdy[j] = 0.f;
+        if (!(m2 & (1 << j))) fdy2[j] = 0.f;
+      }
+    } else {
+      ushort8 vy = y[off];
+      ushort8 vy2 = has2 ? y[off2] : ushort8{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (!(bf2f(vy[j]) > 0.f)) fdy[j] = 0.f;
+        if (!(bf2f(vy2[j]) > 0.f)) fdy2[j] = 0.f;
+      }
+    }
+  }
+  // roundings spelled out as bn_partials_k<1> compiles them (one fma per
+  // channel: dy·x̂ + the second row's rounded product), so the contraction
+  // does not depend on the surrounding code
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    a0[j] += fdy[j] + fdy2[j];
+    float xh = __fmul_rn(__fsub_rn(fx[j], mn[j]), is[j]);
+    float xh2 = __fmul_rn(__fsub_rn(fx2[j], mn[j]), is[j]);
+    a1[j] = __fadd_rn(a1[j], __fmaf_rn(fdy[j], xh, __fmul_rn(fdy2[j], xh2)));
+  }
+}
+
+// block reduce across row lanes via LDS, row lane 0 stores the slab entry
+DEV_INLINE void bn_block_store(float *a0, float *a1,
+                               float *__restrict__ partial, int C8, int cb,
+                               int row_lane, int rows_per_block) {
+  int C = C8 * 8;
+  __shared__ float lds[2][256 * 8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    lds[0][threadIdx.x * 8 + j] = a0[j];
+    lds[1][threadIdx.x * 8 + j] = a1[j];
+  }
+  __syncthreads();
+  if (row_lane == 0) {
+    for (int rl = 1; rl < rows_per_block; ++rl) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        a0[j] += lds[0][(rl * C8 + cb) * 8 + j];
+        a1[j] += lds[1][(rl * C8 + cb) * 8 + j];
+      }
+    }
+    float *p0 = partial + (long)blockIdx.x * 2 * C + cb * 8;
+    float *p1 = p0 + C;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      p0[j] = a0[j];
+      p1[j] = a1[j];
+    }
+  }
+}
+
+// Split-K reduce fused with the BN partials pass, in bn_partials_k's exact
+// geometry (a thread owns one 8-channel group, the block strides over rows,
+// grid from bn_geom). Per row: sum the `splits` fp32 slabs in
+// splitk_reduce_k's order, round ONCE to bf16, write the tensor, and
+// accumulate the statistics of the ROUNDED values — so the tensor is
+// bit-identical to splitk_reduce's and the slab to bn_partials_k's, while
+// the activation is never re-read.
+//   WHAT 0 (forward):  out = conv output y;  slab = Σy, Σy²
+//   WHAT 1 (backward): out = dgrad output dy; slab = Σ(dy·m), Σ(dy·m·x̂)
+//     with x = the consumer BN's saved pre-BN activation.
+template <int WHAT, int SPLITS>
+__global__ void bn_reduce_stats_k(const float4v *__restrict__ slabs,
+                                  int splits_rt, long len4,
+                                  ushort8 *__restrict__ out,
+                                  const ushort8 *__restrict__ x,
+                                  const ushort8 *__restrict__ y,
+                                  const uint8_t *__restrict__ mask,
+                                  const float *__restrict__ mean,
+                                  const float *__restrict__ invstd,
+                                  float *__restrict__ partial, // [grid][2][C]
+                                  long M, int C8, int relu) {
+  int cb = threadIdx.x % C8;
+  int row_lane = threadIdx.x / C8;
+  int rows_per_block = blockDim.x / C8;
+  float a0[8] = {0}, a1[8] = {0};
+  float mn[8], is[8];
+  if (WHAT == 1 && row_lane < rows_per_block) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      mn[j] = mean[cb * 8 + j];
+      is[j] = invstd[cb * 8 + j];
+    }
+  }
+  if (row_lane < rows_per_block) {
+    long stride = (long)gridDim.x * rows_per_block;
+    for (long row = (long)blockIdx.x * rows_per_block + row_lane; row < M;
+         row += 2 * stride) {
+      long r2 = row + stride;
+      bool has2 = r2 < M;
+      long off = row * C8 + cb, off2 = r2 * C8 + cb;
+      // 8 channels = two float4 slab lanes per row; both rows' chains issue
+      // before either is consumed
+      float4v s0 = splitk_sum4<SPLITS>(slabs, splits_rt, len4, off * 2);
+      float4v s1 = splitk_sum4<SPLITS>(slabs, splits_rt, len4, off * 2 + 1);
+      float4v t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
+      if (has2) {
+        t0 = splitk_sum4<SPLITS>(slabs, splits_rt, len4, off2 * 2);
+        t1 = splitk_sum4<SPLITS>(slabs, splits_rt, len4, off2 * 2 + 1);
+      }
+      ushort8 vo, vo2 = ushort8{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        vo[j] = f2bf(s0[j]);
+        vo[4 + j] = f2bf(s1[j]);
+      }
+      out[off] = vo;
+      if (has2) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          vo2[j] = f2bf(t0[j]);
+          vo2[4 + j] = f2bf(t1[j]);
+        }
+        out[off2] = vo2;
+      }
+      float fo[8], fo2[8];
+      bf8_to_f8(vo, fo);
+      bf8_to_f8(vo2, fo2);
+      if (WHAT == 0) {
+        bn_acc_fwd(a0, a1, fo, fo2);
+      } else {
+        float fx[8], fx2[8];
+        ushort8 vx = x[off];
+        ushort8 vx2 = has2 ? x[off2] : ushort8{0, 0, 0, 0, 0, 0, 0, 0};
+        bf8_to_f8(vx, fx);
+        bf8_to_f8(vx2, fx2);
+        bn_acc_bwd(a0, a1, fx, fx2, fo, fo2, y, mask, off, off2, has2, relu,
+                   mn, is);
+      }
+    }
+  }
+  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block);
+}
+
 // finalize: 8 lanes cooperate per channel (grid entries split across lanes,
 // shfl-reduced) — the serial-per-channel version was one-wave latency-bound
 // at 124 µs/call and 31% of the whole step.
@@ -514,6 +679,83 @@ extern "C" hipError_t bn_bwd_launch(const void *dy, const void *x,
   HIP_KERNEL_CHECK();
   bn_finalize_bwd_bands_k<<<C, 256, 0, s>>>(
       partial, grid, C, gamma, invstd, 1.f / (float)M, dbeta, dgamma, k1, k2, k3);
+  HIP_KERNEL_CHECK();
+  bn_bwd_apply_k<<<bn_apply_grid(M, C8), 256, 0, s>>>(
+      (const ushort8 *)dy, (const ushort8 *)x, (const ushort8 *)y, relu_mask,
+      mean, invstd, k1, k2, k3, (ushort8 *)dx, M, C8, relu);
+  HIP_KERNEL_CHECK();
+  return hipSuccess;
+}
+
+// slab rows ([rows][2][C]) of the reduce+stats kernels = the partials grid
+extern "C" int bn_stats_grid(long M, int C) {
+  int grid, rpb;
+  bn_geom(M, C / 8, grid, rpb);
+  return grid;
+}
+
+#define BN_RS_DISPATCH(WHAT, ...)                                              \
+  do {                                                                         \
+    switch (splits) {                                                          \
+    case 2: bn_reduce_stats_k<WHAT, 2><<<grid, 256, 0, s>>>(__VA_ARGS__); break; \
+    case 3: bn_reduce_stats_k<WHAT, 3><<<grid, 256, 0, s>>>(__VA_ARGS__); break; \
+    case 4: bn_reduce_stats_k<WHAT, 4><<<grid, 256, 0, s>>>(__VA_ARGS__); break; \
+    case 5: bn_reduce_stats_k<WHAT, 5><<<grid, 256, 0, s>>>(__VA_ARGS__); break; \
+    case 6: bn_reduce_stats_k<WHAT, 6><<<grid, 256, 0, s>>>(__VA_ARGS__); break; \
+    case 8: bn_reduce_stats_k<WHAT, 8><<<grid, 256, 0, s>>>(__VA_ARGS__); break; \
+    case 16: bn_reduce_stats_k<WHAT, 16><<<grid, 256, 0, s>>>(__VA_ARGS__); break; \
+    default: bn_reduce_stats_k<WHAT, 0><<<grid, 256, 0, s>>>(__VA_ARGS__); break; \
+    }                                                                          \
+  } while (0)
+
+// forward: slabs [splits][M][C] fp32 -> y bf16 + stats slab [grid][2][C]
+extern "C" hipError_t bn_reduce_stats_fwd_launch(const float *slabs,
+                                                 int splits, void *y,
+                                                 float *partial, long M, int C,
+                                                 hipStream_t s) {
+  int C8 = C / 8;
+  if (C8 < 1 || C8 > 256 || C % 8 != 0 || splits < 2)
+    return hipErrorInvalidValue;
+  int grid, rpb;
+  bn_geom(M, C8, grid, rpb);
+  long len4 = M * C / 4;
+  BN_RS_DISPATCH(0, (const float4v *)slabs, splits, len4, (ushort8 *)y,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, partial, M, C8,
+                 0);
+  return hipGetLastError();
+}
+
+// backward: slabs -> dy bf16 + the slab bn_partials_k<1> would produce
+extern "C" hipError_t bn_reduce_stats_bwd_launch(
+    const float *slabs, int splits, void *dy, const void *x, const void *y,
+    const uint8_t *relu_mask, const float *mean, const float *invstd, int relu,
+    float *partial, long M, int C, hipStream_t s) {
+  int C8 = C / 8;
+  if (C8 < 1 || C8 > 256 || C % 8 != 0 || splits < 2)
+    return hipErrorInvalidValue;
+  int grid, rpb;
+  bn_geom(M, C8, grid, rpb);
+  long len4 = M * C / 4;
+  BN_RS_DISPATCH(1, (const float4v *)slabs, splits, len4, (ushort8 *)dy,
+                 (const ushort8 *)x, (const ushort8 *)y, relu_mask, mean,
+                 invstd, partial, M, C8, relu);
+  return hipGetLastError();
+}
+#undef BN_RS_DISPATCH
+
+// bn_bwd starting from a PRE-COMPUTED backward slab (the dgrad split-K
+// reduce's, [pre_grid][2][C]) — skips bn_partials_k<1>'s dy/x re-read.
+extern "C" hipError_t bn_bwd_pre_launch(
+    const float *pre_partial, int pre_grid, const void *dy, const void *x,
+    const void *y, const uint8_t *relu_mask, const float *gamma,
+    const float *mean, const float *invstd, int relu, void *dx, float *dgamma,
+    float *dbeta, float *k1, float *k2, float *k3, long M, int C,
+    hipStream_t s) {
+  int C8 = C / 8;
+  if (C8 < 1 || C8 > 256) return hipErrorInvalidValue;
+  bn_finalize_bwd_bands_k<<<C, 256, 0, s>>>(pre_partial, pre_grid, C, gamma,
+                                            invstd, 1.f / (float)M, dbeta,
+                                            dgamma, k1, k2, k3);
   HIP_KERNEL_CHECK();
   bn_bwd_apply_k<<<bn_apply_grid(M, C8), 256, 0, s>>>(
       (const ushort8 *)dy, (const ushort8 *)x, (const ushort8 *)y, relu_mask,

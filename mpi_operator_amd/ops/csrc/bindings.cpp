@@ -144,8 +144,20 @@ hipError_t conv_dgrad(const void *, const void *, void *, int, int, int, int,
                       int, int, int, int, int, int, int, int, float *,
                       hipStream_t);
 hipError_t conv_fwd_bn(const void *, const void *, void *, int, int, int,
-                       int, int, int, int, int, int, int, int, float *,
-                       hipStream_t);
+                       int, int, int, int, int, int, int, int, int, float *,
+                       float *, hipStream_t);
+int conv_fwd_bn_rows(long, int, int, int, int, int, int, int);
+int conv_dgrad_bn_rows(long, int, int, int, int, int, int);
+hipError_t conv_dgrad_bn(const void *, const void *, void *, int, int, int,
+                         int, int, int, int, int, int, int, int, float *,
+                         const void *, const void *, const uint8_t *,
+                         const float *, const float *, int, float *,
+                         hipStream_t);
+hipError_t bn_bwd_pre_launch(const float *, int, const void *, const void *,
+                             const void *, const uint8_t *, const float *,
+                             const float *, const float *, int, void *,
+                             float *, float *, float *, float *, float *, long,
+                             int, hipStream_t);
 hipError_t bn_fwd_train_pre_launch(const float *, int, const void *,
                                    const void *, const float *, const float *,
                                    float, int, void *, uint8_t *, float *,
@@ -289,10 +301,18 @@ static void conv2d_dgrad_acc(const Tensor &dy, const Tensor &w, Tensor &dx_acc) 
 // ------------------------- batchnorm -------------------------
 // res (optional, may be undefined): residual tensor folded into the apply
 // pass — y = [relu](bn(x) + res), the bottleneck-join fusion.
-// conv forward + fused BN partial stats: returns (y, slab) — slab empty
-// when the shape takes a split-K route (stats would see partial sums).
+// conv forward + fused BN partial stats: returns (y, slab). The slab is
+// [rows][2][Kout] fp32 and bn_fwd_train_pre takes its row count from the
+// tensor: ceil(M/64) bands from the GEMM epilogue on unsplit routes, the
+// partials grid from the reduce+stats kernel on split-K routes. Each kind is
+// produced only when its flag (fuse_epilogue / fuse_splitk) is set. Allocated with at::empty — the kernels write every entry the
+// finalize reads. The slab is EMPTY when no stats were produced (the
+// shape's flag is off, or a route without a stats epilogue): the caller
+// then runs bn_fwd_train.
 static std::vector<Tensor> conv2d_fwd_bn(const Tensor &x, const Tensor &w,
-                                         int64_t stride, int64_t pad) {
+                                         int64_t stride, int64_t pad,
+                                         bool fuse_splitk,
+                                         bool fuse_epilogue) {
   check_cl_bf16(x, "x");
   check_cl_bf16(w, "w");
   const HIPDeviceGuard guard(x.device());
@@ -303,20 +323,76 @@ static std::vector<Tensor> conv2d_fwd_bn(const Tensor &x, const Tensor &w,
   long M = (long)N * HO * WO;
   int splits = conv_splits(M, Kout, R * S * C);
   auto f32 = x.options().dtype(at::kFloat);
-  if (splits > 1 || Kout % 8 != 0) {
+  long rows = Kout % 8 != 0 ? 0
+                            : conv_fwd_bn_rows(M, C, Kout, R, S, (int)stride,
+                                               (int)pad, splits);
+  if (rows == 0 || (splits > 1 ? !fuse_splitk : !fuse_epilogue)) {
     Tensor y = conv2d_fwd(x, w, stride, pad);
     return {y, at::empty({0}, f32)};
   }
+  TORCH_CHECK(w.size(1) == C, "conv channel mismatch");
+  TORCH_CHECK(C % 8 == 0, "conv requires C%8==0 (pad the stem input)");
   Tensor y = empty_cl_bf16(N, Kout, HO, WO, x);
-  long bands = (M + 63) / 64;
-  Tensor slab = at::empty({bands, 2, (long)Kout}, f32);
+  Tensor slab = at::empty({rows, 2, (long)Kout}, f32);
+  Tensor partial;
+  float *pp = nullptr;
+  if (splits > 1) {
+    partial = at::empty({(long)splits, M, (long)Kout}, f32);
+    pp = partial.data_ptr<float>();
+  }
   CHK(conv_fwd_bn(x.data_ptr(), w.data_ptr(), y.data_ptr(), N, H, W, C, Kout,
-                  R, S, (int)stride, (int)pad, HO, WO,
+                  R, S, (int)stride, (int)pad, HO, WO, splits, pp,
                   slab.data_ptr<float>(), cur_stream()));
   return {y, slab};
 }
 
-// bn_fwd_train consuming the conv epilogue's stats slab (skips partials)
+// stride-1 dgrad whose split-K reduce also emits the BN-backward partial
+// stats of the BN layer consuming the result as its dy (bx/by/mask/mean/
+// invstd are that layer's saved tensors): returns (dy, slab [rows][2][C]).
+// The slab is EMPTY when the dgrad does not split (or stride 2): the result
+// is then conv2d_dgrad's and the caller runs bn_bwd.
+static std::vector<Tensor> conv2d_dgrad_bn(
+    const Tensor &dy, const Tensor &w, int64_t H, int64_t W, int64_t stride,
+    int64_t pad, const Tensor &bx, const Tensor &by, const Tensor &mean,
+    const Tensor &invstd, bool relu, const Tensor &mask) {
+  check_cl_bf16(dy, "dy");
+  check_cl_bf16(w, "w");
+  const HIPDeviceGuard guard(dy.device());
+  int N = dy.size(0), Kout = dy.size(1), HO = dy.size(2), WO = dy.size(3);
+  int C = w.size(1), R = w.size(2), S = w.size(3);
+  long M = (long)N * H * W;
+  auto f32 = dy.options().dtype(at::kFloat);
+  int splits = stride == 1 ? conv_splits(M, C, R * S * Kout) : 1;
+  long rows = (Kout % 8 != 0 || C % 8 != 0)
+                  ? 0
+                  : conv_dgrad_bn_rows(M, C, Kout, R, S, (int)stride, splits);
+  if (rows == 0) return {conv2d_dgrad(dy, w, H, W, stride, pad), at::empty({0}, f32)};
+  check_cl_bf16(bx, "bx");
+  TORCH_CHECK(bx.size(0) == N && bx.size(1) == C && bx.size(2) == H &&
+                  bx.size(3) == W, "bx must have the dgrad output's shape");
+  TORCH_CHECK(mean.numel() == C && invstd.numel() == C, "mean/invstd shape");
+  const uint8_t *mp = nullptr;
+  if (mask.defined() && mask.numel() > 0) {
+    TORCH_CHECK(mask.numel() == M * (C / 8), "mask shape");
+    mp = mask.data_ptr<uint8_t>();
+  }
+  if (relu && !mp) {
+    check_cl_bf16(by, "by");
+    TORCH_CHECK(by.numel() == bx.numel(), "by shape");
+  }
+  Tensor dx = empty_cl_bf16(N, C, H, W, dy);
+  Tensor partial = at::empty({(long)splits, M, (long)C}, f32);
+  Tensor slab = at::empty({rows, 2, (long)C}, f32);
+  CHK(conv_dgrad_bn(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), N, (int)H,
+                    (int)W, C, Kout, R, S, (int)pad, HO, WO, splits,
+                    partial.data_ptr<float>(), bx.data_ptr(),
+                    by.defined() && by.numel() > 0 ? by.data_ptr() : nullptr, mp, mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                    relu ? 1 : 0, slab.data_ptr<float>(), cur_stream()));
+  return {dx, slab};
+}
+
+// bn_fwd_train consuming a pre-computed stats slab [rows][2][C] (skips
+// partials); the row count travels with the tensor
 static std::vector<Tensor> bn_fwd_train_pre(
     const Tensor &x, const Tensor &slab, const Tensor &gamma,
     const Tensor &beta, double eps, bool relu, const Tensor &running_mean,
@@ -325,7 +401,9 @@ static std::vector<Tensor> bn_fwd_train_pre(
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   long M = (long)N * H * W;
-  TORCH_CHECK(slab.numel() == ((M + 63) / 64) * 2 * (long)C, "slab shape");
+  TORCH_CHECK(slab.dim() == 3 && slab.size(0) >= 1 && slab.size(1) == 2 &&
+                  slab.size(2) == C && slab.is_contiguous() &&
+                  slab.scalar_type() == at::kFloat, "slab must be [rows][2][C] fp32");
   auto f32 = x.options().dtype(at::kFloat);
   Tensor y = empty_cl_bf16(N, C, H, W, x);
   Tensor mean = at::empty({C}, f32), invstd = at::empty({C}, f32);
@@ -347,7 +425,7 @@ static std::vector<Tensor> bn_fwd_train_pre(
     mask = at::empty({0}, x.options().dtype(at::kByte));
   }
   CHK(bn_fwd_train_pre_launch(
-      slab.data_ptr<float>(), (int)((M + 63) / 64), x.data_ptr(), resp,
+      slab.data_ptr<float>(), (int)slab.size(0), x.data_ptr(), resp,
       gamma.data_ptr<float>(), beta.data_ptr<float>(), (float)eps,
       relu ? 1 : 0, y.data_ptr(), mp, mean.data_ptr<float>(),
       invstd.data_ptr<float>(), scale.data_ptr<float>(),
@@ -429,6 +507,36 @@ static std::vector<Tensor> bn_bwd(const Tensor &dy, const Tensor &x,
                     k1.data_ptr<float>(), k2.data_ptr<float>(),
                     k3.data_ptr<float>(), partial.data_ptr<float>(), M, C,
                     cur_stream()));
+  return {dx, dgamma, dbeta};
+}
+
+// bn_bwd starting from the dgrad reduce's backward slab [rows][2][C]
+static std::vector<Tensor> bn_bwd_pre(const Tensor &dy, const Tensor &slab,
+                                      const Tensor &x, const Tensor &y,
+                                      const Tensor &gamma, const Tensor &mean,
+                                      const Tensor &invstd, bool relu,
+                                      const Tensor &mask) {
+  check_cl_bf16(dy, "dy");
+  check_cl_bf16(x, "x");
+  const HIPDeviceGuard guard(x.device());
+  int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  long M = (long)N * H * W;
+  TORCH_CHECK(slab.dim() == 3 && slab.size(0) >= 1 && slab.size(1) == 2 &&
+                  slab.size(2) == C && slab.is_contiguous() &&
+                  slab.scalar_type() == at::kFloat, "slab must be [rows][2][C] fp32");
+  auto f32 = x.options().dtype(at::kFloat);
+  Tensor dx = empty_cl_bf16(N, C, H, W, x);
+  Tensor dgamma = at::empty({C}, f32), dbeta = at::empty({C}, f32);
+  Tensor k1 = at::empty({C}, f32), k2 = at::empty({C}, f32), k3 = at::empty({C}, f32);
+  const uint8_t *mp =
+      mask.defined() && mask.numel() > 0 ? mask.data_ptr<uint8_t>() : nullptr;
+  CHK(bn_bwd_pre_launch(slab.data_ptr<float>(), (int)slab.size(0),
+                        dy.data_ptr(), x.data_ptr(), y.data_ptr(), mp,
+                        gamma.data_ptr<float>(), mean.data_ptr<float>(),
+                        invstd.data_ptr<float>(), relu ? 1 : 0, dx.data_ptr(),
+                        dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
+                        k1.data_ptr<float>(), k2.data_ptr<float>(),
+                        k3.data_ptr<float>(), M, C, cur_stream()));
   return {dx, dgamma, dbeta};
 }
 
@@ -977,7 +1085,11 @@ static Tensor gemm_nt_b(const Tensor &a, const Tensor &b, bool c_f32) {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd", &conv2d_fwd);
   m.def("conv2d_dgrad", &conv2d_dgrad);
-  m.def("conv2d_fwd_bn", &conv2d_fwd_bn);
+  m.def("conv2d_fwd_bn", &conv2d_fwd_bn, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("pad"), py::arg("fuse_splitk") = true,
+        py::arg("fuse_epilogue") = true);
+  m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
+  m.def("bn_bwd_pre", &bn_bwd_pre);
   m.def("bn_fwd_train_pre", &bn_fwd_train_pre);
   m.def("conv2d_wgrad", &conv2d_wgrad);
   m.def("conv2d_dgrad_acc", &conv2d_dgrad_acc);

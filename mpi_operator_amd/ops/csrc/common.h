@@ -59,7 +59,45 @@ DEV_INLINE float wave_max(float v) {
   return v;
 }
 
-#define HIP_KERNEL_CHECK()                                                    \
+// Sum of the `splits` fp32 split-K slabs at float4 index i — THE summation
+// order of every split-K reduce here (a = p0, then slab pairs alternately
+// into a and b, then a += b), shared by splitk_reduce_k and the
+// reduce+BN-stats kernels so their outputs are bit-identical. SPLITS is a
+// template parameter for the common counts so the loop FULLY UNROLLS; the
+// runtime-count form (SPLITS == 0, wgrad runs 24..256) keeps 8 independent
+// loads in flight through fixed 8-deep chunks — the plain runtime loop
+// issued a 2-chain serial walk and sat 73% wave-parked.
+template <int SPLITS>
+DEV_INLINE float4v splitk_sum4(const float4v *__restrict__ partial,
+                               int splits_rt, long len4, long i) {
+  const int splits = SPLITS ? SPLITS : splits_rt;
+  float4v a = partial[i];
+  float4v b = {0.f, 0.f, 0.f, 0.f};
+  int s = 1;
+  if (SPLITS == 0) {
+    for (; s + 8 <= splits; s += 8) {
+      float4v c0 = {0.f, 0.f, 0.f, 0.f};
+      float4v c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 8; j += 2) {
+        c0 += partial[(long)(s + j) * len4 + i];
+        c1 += partial[(long)(s + j + 1) * len4 + i];
+      }
+      a += c0;
+      b += c1;
+    }
+  }
+#pragma unroll
+  for (; s + 1 < splits; s += 2) {
+    a += partial[(long)s * len4 + i];
+    b += partial[(long)(s + 1) * len4 + i];
+  }
+  if (s < splits) b += partial[(long)s * len4 + i];
+  a += b;
+  return a;
+}
+
+#define HIP_KERNEL_CHECK()                                                   \
   do {                                                                        \
     hipError_t e = hipGetLastError();                                         \
     if (e != hipSuccess) return e;                                            \

@@ -198,14 +198,18 @@ struct XcolStage {
 // Late-stage convs have few 128x128 output tiles (7x7 spatial: ~100 blocks
 // on 256 CUs): when `splits` > 1 the GEMM runs split-K into the caller's
 // fp32 slab and splitk_reduce emits bf16 — same scheme as wgrad.
-extern "C" hipError_t conv_fwd(const void *x, const void *w, void *y, int N,
-                               int H, int W, int C, int Kout, int R, int S,
-                               int stride, int pad, int HO, int WO, int splits,
-                               float *partial, hipStream_t strm) {
+// `reduce` false leaves the split-K slabs unreduced (the BN-stats reduce in
+// batchnorm.hip consumes them); *splits_out gets the clamped split count.
+static hipError_t conv_fwd_impl(const void *x, const void *w, void *y, int N,
+                                int H, int W, int C, int Kout, int R, int S,
+                                int stride, int pad, int HO, int WO,
+                                int splits, float *partial, bool reduce,
+                                int *splits_out, hipStream_t strm) {
   long M = (long)N * HO * WO;
   int K = R * S * C;
   int nk = (K + BK - 1) / BK;
   if (splits > nk) splits = nk > 0 ? nk : 1;
+  if (splits_out) *splits_out = splits;
   void *out = splits > 1 ? (void *)partial : y;
   bool f32 = splits > 1;
   hipError_t e;
@@ -229,37 +233,95 @@ extern "C" hipError_t conv_fwd(const void *x, const void *w, void *y, int N,
     e = launch_mix_gemm(sa, NtStage<GemmLoader>{lb}, out, (int)M, Kout, K,
                         Kout, f32, strm, splits);
   }
-  if (e != hipSuccess || splits <= 1) return e;
+  if (e != hipSuccess || splits <= 1 || !reduce) return e;
   return splitk_reduce(partial, splits, M * Kout, y, 1, strm);
 }
 
-// conv forward that ALSO emits BatchNorm partial statistics from the GEMM
-// epilogue (BnStatsWriter slab [ceil(M/64)][2][Kout]). splits==1 only —
-// the caller (bindings conv2d_fwd_bn) checks and falls back otherwise.
+extern "C" hipError_t conv_fwd(const void *x, const void *w, void *y, int N,
+                               int H, int W, int C, int Kout, int R, int S,
+                               int stride, int pad, int HO, int WO, int splits,
+                               float *partial, hipStream_t strm) {
+  return conv_fwd_impl(x, w, y, N, H, W, C, Kout, R, S, stride, pad, HO, WO,
+                       splits, partial, true, nullptr, strm);
+}
+
+// conv forward that ALSO emits BatchNorm partial statistics. It runs
+// EXACTLY the GEMM kernel conv_fwd runs for the same shape and environment
+// (turning the fusion on never changes the route):
+//   splits == 1: stats from the GEMM epilogue — BnStatsWriter slab
+//     [ceil(M/64)][2][Kout].
+//   splits  > 1: split-K GEMM into `partial`, then the reduce+stats kernel
+//     (batchnorm.hip) writes y and a [bn partials grid][2][Kout] slab.
+// conv_fwd_bn_rows() tells the caller how many slab rows to allocate; 0
+// means this shape's route has no stats epilogue (the BK=32 256² kernel) and
+// the caller must take the unfused pair.
+extern "C" int bn_stats_grid(long M, int C);
+extern "C" hipError_t bn_reduce_stats_fwd_launch(const float *, int, void *,
+                                                 float *, long, int,
+                                                 hipStream_t);
+extern "C" hipError_t bn_reduce_stats_bwd_launch(
+    const float *, int, void *, const void *, const void *, const uint8_t *,
+    const float *, const float *, int, float *, long, int, hipStream_t);
+
+static bool conv_is_plain_1x1(int R, int S, int stride, int pad) {
+  return R == 1 && S == 1 && stride == 1 && pad == 0;
+}
+
+extern "C" int conv_fwd_bn_rows(long M, int C, int Kout, int R, int S,
+                                int stride, int pad, int splits) {
+  int K = R * S * C;
+  int nk = (K + BK - 1) / BK;
+  if (splits > nk) splits = nk > 0 ? nk : 1;
+  if (splits > 1) return bn_stats_grid(M, Kout);
+  if (conv_is_plain_1x1(R, S, stride, pad) &&
+      nt_gemm_route((int)M, Kout, C, Kout, C, C, 1) == NT_256)
+    return 0;
+  return (int)((M + 63) / 64);
+}
+
 extern "C" hipError_t conv_fwd_bn(const void *x, const void *w, void *y,
                                   int N, int H, int W, int C, int Kout, int R,
                                   int S, int stride, int pad, int HO, int WO,
-                                  float *bn_slab, hipStream_t strm) {
+                                  int splits, float *partial, float *bn_slab,
+                                  hipStream_t strm) {
   long M = (long)N * HO * WO;
   int K = R * S * C;
+  int nk = (K + BK - 1) / BK;
+  if (splits > nk) splits = nk > 0 ? nk : 1;
+  if (splits > 1) {
+    int sp = splits;
+    hipError_t e = conv_fwd_impl(x, w, y, N, H, W, C, Kout, R, S, stride, pad,
+                                 HO, WO, splits, partial, false, &sp, strm);
+    if (e != hipSuccess) return e;
+    return bn_reduce_stats_fwd_launch(partial, sp, y, bn_slab, M, Kout, strm);
+  }
   BnStatsWriter wrt{(long)Kout, bn_slab, Kout};
-  if (R == 1 && S == 1 && stride == 1 && pad == 0) {
+  if (conv_is_plain_1x1(R, S, stride, pad)) {
     GemmLoader la{(const uint16_t *)x, (int)M, (long)C, C};
     GemmLoader lb{(const uint16_t *)w, Kout, (long)C, C};
-    if (M % 256 == 0 && Kout % 256 == 0 && C % 64 == 0 &&
-        (long)(M / 256) * (Kout / 256) >= 128)
+    switch (nt_gemm_route((int)M, Kout, C, Kout, C, C, 1)) {
+    case NT_PIPE256:
       return launch_pipe256_wr(la, lb, y, (int)M, Kout, C, Kout, false, wrt,
                                strm);
-    if (use_pipemix()) {
+    case NT_256:
+      return hipErrorInvalidValue; // caller contract: conv_fwd_bn_rows() == 0
+    case NT_PIPEMIX: {
       NtPipe<PlainNtSrc> sa{{(const uint16_t *)x, (long)C, (int)M, C}};
       NtPipe<PlainNtSrc> sb{{(const uint16_t *)w, (long)C, Kout, C}};
       return launch_pipe_mix_wr(sa, sb, y, (int)M, Kout, C, wrt, Kout, false,
                                 strm);
     }
-    GldsNt ga{la.p, la.rows, la.ld, la.kdim};
-    GldsNt gb{lb.p, lb.rows, lb.ld, lb.kdim};
-    return launch_mix_gemm_wr(ga, gb, y, (int)M, Kout, C, wrt, Kout, false,
-                              strm);
+    case NT_GLDS: {
+      GldsNt ga{la.p, la.rows, la.ld, la.kdim};
+      GldsNt gb{lb.p, lb.rows, lb.ld, lb.kdim};
+      return launch_mix_gemm_wr(ga, gb, y, (int)M, Kout, C, wrt, Kout, false,
+                                strm);
+    }
+    default:
+      return launch_mix_gemm_wr(NtStage<GemmLoader>{la},
+                                NtStage<GemmLoader>{lb}, y, (int)M, Kout, C,
+                                wrt, Kout, false, strm);
+    }
   }
   if (use_pipegather()) {
     NtPipe<ConvFwdSrc> sa{
@@ -455,17 +517,18 @@ static hipError_t conv_dgrad_s2(const void *dy, const void *w, void *dx,
 
 // dgrad: w used directly (channels_last [Kout][RSC]); the k-strided B view
 // w[q][rs·C + c0..7] is transposed in the LDS write pass (TN staging).
-extern "C" hipError_t conv_dgrad(const void *dy, const void *w, void *dx,
-                                 int N, int H, int W, int C, int Kout, int R,
-                                 int S, int stride, int pad, int HO, int WO,
-                                 int splits, float *partial,
-                                 hipStream_t strm) {
+static hipError_t conv_dgrad_impl(const void *dy, const void *w, void *dx,
+                                  int N, int H, int W, int C, int Kout, int R,
+                                  int S, int stride, int pad, int HO, int WO,
+                                  int splits, float *partial, bool reduce,
+                                  int *splits_out, hipStream_t strm) {
   long M = (long)N * H * W;
   int K = R * S * Kout;
   if (stride != 1)
     return conv_dgrad_s2(dy, w, dx, N, H, W, C, Kout, R, S, pad, HO, WO, strm);
   int nk = (K + BK - 1) / BK;
   if (splits > nk) splits = nk > 0 ? nk : 1;
+  if (splits_out) *splits_out = splits;
   void *out = splits > 1 ? (void *)partial : dx;
   bool f32 = splits > 1;
   hipError_t e;
@@ -495,9 +558,54 @@ extern "C" hipError_t conv_dgrad(const void *dy, const void *w, void *dx,
     e = launch_mix_gemm(sa, TnStage<DgradWTn>{lb}, out, (int)M, C, K, C, f32,
                         strm, splits);
   }
-  if (e != hipSuccess || splits <= 1) return e;
+  if (e != hipSuccess || splits <= 1 || !reduce) return e;
   return splitk_reduce(partial, splits, M * C, dx, 1, strm);
 }
+
+extern "C" hipError_t conv_dgrad(const void *dy, const void *w, void *dx,
+                                 int N, int H, int W, int C, int Kout, int R,
+                                 int S, int stride, int pad, int HO, int WO,
+                                 int splits, float *partial,
+                                 hipStream_t strm) {
+  return conv_dgrad_impl(dy, w, dx, N, H, W, C, Kout, R, S, stride, pad, HO,
+                         WO, splits, partial, true, nullptr, strm);
+}
+
+// Slab rows of the split-K dgrad + BN-backward-stats pair, 0 when this
+// dgrad does not split (stride 2, or splits clamp to 1): the caller keeps
+// conv_dgrad + bn_bwd there.
+extern "C" int conv_dgrad_bn_rows(long M, int C, int Kout, int R, int S,
+                                  int stride, int splits) {
+  int K = R * S * Kout;
+  int nk = (K + BK - 1) / BK;
+  if (splits > nk) splits = nk > 0 ? nk : 1;
+  if (stride != 1 || splits <= 1) return 0;
+  return bn_stats_grid(M, C);
+}
+
+// Stride-1 split-K dgrad whose reduce also emits the BN-backward partial
+// statistics of the layer that consumes dx as its dy: the reduce reads
+// that layer's saved pre-BN activation bx (+ ReLU mask or output by, mean,
+// invstd) and writes the Σ(dy·m), Σ(dy·m·x̂) slab bn_partials_k<1> would
+// produce from the rounded dx — same geometry, same order.
+extern "C" hipError_t conv_dgrad_bn(const void *dy, const void *w, void *dx,
+                                    int N, int H, int W, int C, int Kout,
+                                    int R, int S, int pad, int HO, int WO,
+                                    int splits, float *partial, const void *bx,
+                                    const void *by, const uint8_t *mask,
+                                    const float *mean, const float *invstd,
+                                    int relu, float *bn_slab,
+                                    hipStream_t strm) {
+  long M = (long)N * H * W;
+  int sp = splits;
+  hipError_t e = conv_dgrad_impl(dy, w, dx, N, H, W, C, Kout, R, S, 1, pad, HO,
+                                 WO, splits, partial, false, &sp, strm);
+  if (e != hipSuccess) return e;
+  if (sp <= 1) return hipErrorInvalidValue; // conv_dgrad_bn_rows() == 0
+  return bn_reduce_stats_bwd_launch(partial, sp, dx, bx, by, mask, mean,
+                                    invstd, relu, bn_slab, M, C, strm);
+}
+
 
 // float4 lanes; SPLITS is a template parameter for the common counts so
 // the accumulation loop FULLY UNROLLS — the runtime-splits version issued
@@ -507,35 +615,10 @@ template <bool OUT_BF16, int SPLITS = 0>
 __global__ void splitk_reduce_k(const float4v *__restrict__ partial,
                                 int splits_rt, long len4,
                                 void *__restrict__ out) {
-  const int splits = SPLITS ? SPLITS : splits_rt;
   for (long i = blockIdx.x * blockDim.x + threadIdx.x; i < len4;
        i += (long)gridDim.x * blockDim.x) {
-    float4v a = partial[i];
-    float4v b = {0.f, 0.f, 0.f, 0.f};
-    int s = 1;
-    if (SPLITS == 0) {
-      // runtime split count (wgrad runs 24..256): fixed 8-deep inner
-      // chunks keep 8 independent loads in flight — the plain runtime
-      // loop issued a 2-chain serial walk and sat 73% wave-parked
-      for (; s + 8 <= splits; s += 8) {
-        float4v c0 = {0.f, 0.f, 0.f, 0.f};
-        float4v c1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-          c0 += partial[(long)(s + j) * len4 + i];
-          c1 += partial[(long)(s + j + 1) * len4 + i];
-        }
-        a += c0;
-        b += c1;
-      }
-    }
-#pragma unroll
-    for (; s + 1 < splits; s += 2) {
-      a += partial[(long)s * len4 + i];
-      b += partial[(long)(s + 1) * len4 + i];
-    }
-    if (s < splits) b += partial[(long)s * len4 + i];
-    a += b;
+    // summation order lives in common.h (shared with the BN-stats reduces)
+    float4v a = splitk_sum4<SPLITS>(partial, splits_rt, len4, i);
     if (OUT_BF16) {
       uint16_t *o = (uint16_t *)out + i * 4;
 #pragma unroll

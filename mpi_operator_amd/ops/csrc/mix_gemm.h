@@ -283,33 +283,48 @@ struct GeluBwdPreWriter {
 // activation it just wrote (~9% of a ResNet step at 8 TB/s).
 //
 // Deterministic, atomic-free: the slab has one entry per 64 OUTPUT ROWS
-// ([ceil(M/64)][2][C], pre-zeroed by the host). In every tile kernel here
-// (mix/pipe_mix 2×2 waves, pipe256 2×4) a lane's epilogue rows all fall in
-// ONE 64-row band per m-frag half, and a (band, channel) pair is written
-// by exactly one lane pair (l, l^32) — combined with one shfl, stored
-// plain. Stats use the ROUNDED bf16 value (what bn_partials would read).
+// ([ceil(M/64)][2][C], allocated UNINITIALIZED by the host: every band has
+// at least one valid row and its first row belongs to a lane < 32, so each
+// (band, channel < C) entry the finalize reads is written — ragged last
+// band and ragged last column tile included). In every tile kernel here
+// (mix/pipe_mix 2×2 waves, pipe_mix8 2×4 waves, pipe256) a lane's epilogue
+// rows all fall in ONE 64-row band per m-frag half, and a (band, channel)
+// pair is written by exactly one lane pair (l, l^32) — combined with one
+// shfl, stored plain. Stats use the ROUNDED bf16 value (what bn_partials
+// would read).
+//
+// Accumulators are addressed by a SLOT the kernel names with its unrolled
+// loop indices — slot(band, colslot), both compile-time constants after
+// unrolling — never by values derived from row/col: runtime-indexed
+// accumulator arrays went to scratch memory (80 B/lane, one scratch
+// read-modify-write per stored element; the 256² kernel ran 48 vs 18 us).
+// band: which of the lane's (at most two) 64-row bands the m-frag is in;
+// colslot: which of the lane's (at most two) columns.
 struct BnStatsWriter {
   static constexpr bool ACC = false;
   static constexpr bool STATS = true;
   long ldc;
   float *slab; // [ceil(M/64)][2][C]
   int C;
-  // mutable per-lane accumulators: [row-band half][col slot (bit5 of col)]
+  // mutable per-lane accumulators: [band slot][col slot]
   mutable float s0[2][2], s1[2][2];
   mutable int tm[2], colc[2];
-  mutable int half_;
+  mutable int h_, c_, band_;
   typedef long RowCtx;
   DEV_INLINE void reset() const {
     s0[0][0] = s0[0][1] = s0[1][0] = s0[1][1] = 0.f;
     s1[0][0] = s1[0][1] = s1[1][0] = s1[1][1] = 0.f;
     tm[0] = tm[1] = -1;
     colc[0] = colc[1] = -1;
-    half_ = 0;
+    h_ = c_ = 0;
+    band_ = -1;
+  }
+  DEV_INLINE void slot(int band, int colslot) const {
+    h_ = band;
+    c_ = colslot;
   }
   DEV_INLINE RowCtx row_ctx(int row) const {
-    // pipe256's 4 m-frags span two 64-row bands per lane; track which
-    half_ = (row >> 6) & 1;
-    tm[half_] = row >> 6;
+    band_ = row >> 6;
     return (long)row * ldc;
   }
   DEV_INLINE void store_f32(float *p, RowCtx b, int col, float v) const {
@@ -319,15 +334,16 @@ struct BnStatsWriter {
     uint16_t r = f2bf(v);
     p[b + col] = r;
     float vr = bf2f(r);
-    int ci = (col >> 5) & 1;
-    colc[ci] = col;
-    s0[half_][ci] += vr;
-    s1[half_][ci] += vr * vr;
+    tm[h_] = band_;
+    colc[c_] = col;
+    s0[h_][c_] += vr;
+    s1[h_][c_] += vr * vr;
   }
   DEV_INLINE void flush(int lane) const {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       // bands are per-(lane-half) identical; tm/col agree across l, l^32
+      // wherever both lanes stored (the lane < 32 owns the band's first row)
 #pragma unroll
       for (int ci = 0; ci < 2; ++ci) {
         float a = s0[h][ci] + __shfl_xor(s0[h][ci], 32, 64);
@@ -525,6 +541,7 @@ __global__ __launch_bounds__(NT_THREADS) void mix_gemm_k(
       for (int ni = 0; ni < 2; ++ni) {
         int col = col0 + wc * 64 + ni * 32 + (lane & 31);
         if (col >= N) continue;
+        if constexpr (WR::STATS) wrt.slot(0, ni); // both m-frags: one band
         if (C_F32)
           wrt.store_f32((float *)cptr, rc, col, acc[mi][ni][r]);
         else
@@ -603,11 +620,12 @@ static hipError_t launch_mix_gemm(const SA &sa, const SB &sb, void *c, int M,
 // vs register staging selectable for same-box A/B (MPIAMD_GLDS=0 reverts).
 // Full-tile shapes take the 256²-tile counted-vmcnt pipeline (gemm256.h);
 // MPIAMD_GEMM256=0 reverts those to the mix_gemm path.
-template <class LA, class LB>
-static hipError_t launch_nt_gemm(const LA &la, const LB &lb, void *c, int M,
-                                 int N, int K, long ldc, bool c_f32,
-                                 hipStream_t s, int splits = 1,
-                                 const float *bias = nullptr) {
+// Route choice of the plain NT×NT entry, factored out so the BN-stats conv
+// forward (conv.hip conv_fwd_bn) runs exactly the kernel the unfused conv
+// runs for the same shape and environment.
+enum NtRoute { NT_PIPE256, NT_256, NT_PIPEMIX, NT_GLDS, NT_REG };
+static inline NtRoute nt_gemm_route(int M, int N, int K, long ldc, int kdim_a,
+                                    int kdim_b, int splits) {
   static const bool use_256 = [] {
     const char *e = getenv("MPIAMD_GEMM256");
     return !(e && e[0] == '0');
@@ -623,12 +641,9 @@ static hipError_t launch_nt_gemm(const LA &la, const LB &lb, void *c, int M,
     return !(e && e[0] == '0');
   }();
   if (use_256 && splits <= 1 && M % 256 == 0 && N % 256 == 0 && K % 32 == 0 &&
-      K > 0 && la.kdim == K && lb.kdim == K && ldc == N &&
-      (long)(M / 256) * (N / 256) >= 128) {
-    if (use_pipe && K % 64 == 0)
-      return launch_pipe256(la, lb, c, M, N, K, ldc, c_f32, s, bias);
-    return launch_nt256(la, lb, c, M, N, K, ldc, c_f32, s, bias);
-  }
+      K > 0 && kdim_a == K && kdim_b == K && ldc == N &&
+      (long)(M / 256) * (N / 256) >= 128)
+    return (use_pipe && K % 64 == 0) ? NT_PIPE256 : NT_256;
   // non-full-tile / small-grid shapes: the 128²-tile deep pipeline
   // (pipe_mix.h) — ragged edges handled by its zeros-page staging.
   // MPIAMD_PIPENT=0 reverts just this NT fallback (bisect lever).
@@ -636,7 +651,25 @@ static hipError_t launch_nt_gemm(const LA &la, const LB &lb, void *c, int M,
     const char *e = getenv("MPIAMD_PIPENT");
     return !(e && e[0] == '0');
   }();
-  if (use_pipemix() && use_pipent) {
+  if (use_pipemix() && use_pipent) return NT_PIPEMIX;
+  static const bool use_glds = [] {
+    const char *e = getenv("MPIAMD_GLDS");
+    return !(e && e[0] == '0');
+  }();
+  return use_glds ? NT_GLDS : NT_REG;
+}
+
+template <class LA, class LB>
+static hipError_t launch_nt_gemm(const LA &la, const LB &lb, void *c, int M,
+                                 int N, int K, long ldc, bool c_f32,
+                                 hipStream_t s, int splits = 1,
+                                 const float *bias = nullptr) {
+  switch (nt_gemm_route(M, N, K, ldc, la.kdim, lb.kdim, splits)) {
+  case NT_PIPE256:
+    return launch_pipe256(la, lb, c, M, N, K, ldc, c_f32, s, bias);
+  case NT_256:
+    return launch_nt256(la, lb, c, M, N, K, ldc, c_f32, s, bias);
+  case NT_PIPEMIX: {
     NtPipe<PlainNtSrc> ga{{la.p, la.ld, la.rows, la.kdim}};
     NtPipe<PlainNtSrc> gb{{lb.p, lb.ld, lb.rows, lb.kdim}};
     if (bias)
@@ -645,17 +678,16 @@ static hipError_t launch_nt_gemm(const LA &la, const LB &lb, void *c, int M,
     return launch_pipe_mix_wr(ga, gb, c, M, N, K, LinearWriter{ldc}, ldc,
                               c_f32, s, splits);
   }
-  static const bool use_glds = [] {
-    const char *e = getenv("MPIAMD_GLDS");
-    return !(e && e[0] == '0');
-  }();
-  if (use_glds) {
+  case NT_GLDS: {
     GldsNt ga{la.p, la.rows, la.ld, la.kdim};
     GldsNt gb{lb.p, lb.rows, lb.ld, lb.kdim};
     if (bias)
       return launch_mix_gemm_wr(ga, gb, c, M, N, K, BiasWriter{ldc, bias},
                                 ldc, c_f32, s, splits);
     return launch_mix_gemm(ga, gb, c, M, N, K, ldc, c_f32, s, splits);
+  }
+  default:
+    break;
   }
   if (bias)
     return launch_mix_gemm_wr(NtStage<LA>{la}, NtStage<LB>{lb}, c, M, N, K,

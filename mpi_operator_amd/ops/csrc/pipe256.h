@@ -188,6 +188,8 @@ __global__ __launch_bounds__(512) void pipe256_gemm_k(
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
           int col = col0 + wc * 64 + ni * 32 + (lane & 31);
+          // 4 m-frags span two 64-row bands per lane: frags 0,1 | 2,3
+          if constexpr (WR::STATS) wrt.slot(mi >> 1, ni);
           if (C_F32)
             wrt.store_f32((float *)cptr, rc, col, acc[mi][ni][r]);
           else
@@ -334,6 +336,7 @@ __global__ __launch_bounds__(1024) void pipe256x16_gemm_k(
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
           int col = col0 + wc * 64 + ni * 32 + (lane & 31);
+          if constexpr (WR::STATS) wrt.slot(0, ni); // both m-halves: one band
           if (C_F32)
             wrt.store_f32((float *)cptr, rc, col, acc[mh][ni][r]);
           else

@@ -590,6 +590,7 @@ __global__ __launch_bounds__(PM_THREADS) void pipe_mix_k(
       for (int ni = 0; ni < 2; ++ni) {
         int col = col0 + wc * 64 + ni * 32 + (lane & 31);
         if (col >= N) continue;
+        if constexpr (WR::STATS) wrt.slot(0, ni); // both m-frags: one band
         if (C_F32)
           wrt.store_f32((float *)cptr, rc, col, acc[mi][ni][r]);
         else
@@ -640,14 +641,12 @@ static hipError_t launch_pipe_mix_wr(const SA &sa, const SB &sb, void *c,
                                      int M, int N, int K, const WR &wrt,
                                      long ldc, bool c_f32, hipStream_t s,
                                      int splits = 1) {
-  // MPIAMD_PIPE8: route every non-STATS writer through the 8-wave kernel
-  // (the band-slab BnStatsWriter assumes the 2x2 wave structure)
-  if constexpr (!WR::STATS) {
-    if (use_pipe8())
-      return launch_pipe_mix8_wr(typename Pipe8Of<SA>::type{sa.s},
-                                 typename Pipe8Of<SB>::type{sb.s}, c, M, N,
-                                 K, wrt, ldc, c_f32, s, splits);
-  }
+  // MPIAMD_PIPE8: route every writer through the 8-wave kernel (the
+  // band-slab BnStatsWriter holds for both the 2x2 and the 2x4 wave layout)
+  if (use_pipe8())
+    return launch_pipe_mix8_wr(typename Pipe8Of<SA>::type{sa.s},
+                               typename Pipe8Of<SB>::type{sb.s}, c, M, N, K,
+                               wrt, ldc, c_f32, s, splits);
   const uint16_t *zeros = pm_zeros_page();
   if (!zeros) return hipErrorOutOfMemory;
   int tiles_m = (M + PM_BM - 1) / PM_BM, tiles_n = (N + PM_BM - 1) / PM_BM;
@@ -842,12 +841,16 @@ __global__ __launch_bounds__(512) void pipe_mix8_k(
       typename WR::RowCtx rc = wrt.row_ctx(row);
       int col = col0 + wc * 32 + (lane & 31);
       if (col >= N) continue;
+      if constexpr (WR::STATS) wrt.slot(0, 0); // one band, one column
       if (C_F32)
         wrt.store_f32((float *)cptr, rc, col, acc[mi][r]);
       else
         wrt.store_bf16((uint16_t *)cptr, rc, col, acc[mi][r]);
     }
   }
+  // 2×4 layout: a lane owns ONE column and 32 rows of ONE 64-row band
+  // (row0 + wr*64); the lane pair (l, l^32) completes the band
+  if constexpr (WR::STATS) wrt.flush(lane);
 }
 #undef PM8_IMG
 

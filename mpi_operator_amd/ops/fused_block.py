@@ -10,7 +10,9 @@ What the fusion buys over per-op autograd (per block, per step):
     (accumulate writer) — no separate pass;
   - autograd bookkeeping for 6+ interior nodes disappears.
 
-Numerics are identical to the unfused path: same kernels, same order.
+Numerics are identical to the unfused path: same GEMM kernels, same order.
+Only the opt-in epilogue statistics (MPIAMD_FUSEBN_EPI, see below) change the
+fp32 summation order of the forward statistics on unsplit conv routes.
 """
 from __future__ import annotations
 
@@ -20,10 +22,27 @@ from ._backend import hip_ext
 
 import os as _os
 
-# Conv-epilogue BN-stats fusion: measured net-negative same-box (3124 vs
-# 3192 img/s — the epilogue tax on every conv exceeds the removed partials
-# pass at these shapes); default OFF, MPIAMD_FUSEBN=1 enables for A/B.
-_FUSEBN = _os.environ.get("MPIAMD_FUSEBN", "0") == "1"
+# BN-statistics fusion (docs/tuning.md, profiles/BENCH_HISTORY.md).
+#   MPIAMD_FUSEBN         master gate (default on); "0" turns all three
+#                         parts off.
+#   MPIAMD_FUSEBN_EPI     forward Σy/Σy² out of the conv GEMM epilogue on
+#                         every unsplit route (8-wave and 256² kernels
+#                         included). Default OFF: it is faster (+2.2%) but
+#                         reorders the fp32 sums of the statistics, and a
+#                         training trajectory amplifies that to O(1) logit
+#                         differences within ten steps — results must stay
+#                         what they were. "1" enables for A/B.
+#   MPIAMD_FUSEBN_SPLITK  forward split-K convs: the split-K reduce also
+#                         emits the stats slab. Default on: tensor and
+#                         statistics bit-identical to the unfused pair.
+#   MPIAMD_FUSEBN_BWD     backward: the split-K dgrad reduce also emits the
+#                         Σ(dy·m), Σ(dy·m·x̂) slab of the BN that consumes
+#                         it. Default on: bit-identical likewise.
+# The sub-gates only act under the master gate; each is "1"/"0".
+_FUSEBN = _os.environ.get("MPIAMD_FUSEBN", "1") == "1"
+_FUSEBN_EPI = _FUSEBN and _os.environ.get("MPIAMD_FUSEBN_EPI", "0") == "1"
+_FUSEBN_SPLITK = _FUSEBN and _os.environ.get("MPIAMD_FUSEBN_SPLITK", "1") == "1"
+_FUSEBN_BWD = _FUSEBN and _os.environ.get("MPIAMD_FUSEBN_BWD", "1") == "1"
 
 _EMPTY = None
 
@@ -46,15 +65,17 @@ class BottleneckFn(torch.autograd.Function):
         e = _empty()
 
         def conv_bn(xin, w, st, pad, g, b, eps_, relu, rm, rv, mom, res):
-            """conv with BN stats fused into the GEMM epilogue; the empty-
-            slab return (split-K shapes) falls back to the partials pass.
+            """conv with BN stats fused into the GEMM epilogue (unsplit
+            routes) or the split-K reduce; an empty slab (no stats produced
+            for this shape) takes the partials pass.
             Returns the relu bitmask too (backward skips the y re-read)."""
-            if not _FUSEBN:
+            if not (_FUSEBN_EPI or _FUSEBN_SPLITK):
                 a = ext.conv2d_fwd(xin, w, st, pad)
                 y, m, v, mk = ext.bn_fwd_train(a, g, b, eps_, relu, rm, rv,
                                                mom, res)
                 return a, y, m, v, mk
-            a, slab = ext.conv2d_fwd_bn(xin, w, st, pad)
+            a, slab = ext.conv2d_fwd_bn(xin, w, st, pad, _FUSEBN_SPLITK,
+                                        _FUSEBN_EPI)
             if slab.numel() > 0:
                 y, m, v, mk = ext.bn_fwd_train_pre(a, slab, g, b, eps_, relu,
                                                    rm, rv, mom, res)
@@ -97,13 +118,25 @@ class BottleneckFn(torch.autograd.Function):
         # The join's ReLU mask (out > 0) is applied INSIDE each consumer
         # (bn_bwd's relu path reads `out` anyway) — the old materialized
         # g = dout·(out>0) was pure data movement (2 extra passes/block).
+
+        def dgrad_bn(dyo, w, st_, pad, a, y, g, m, v, mk):
+            """dgrad feeding a BN(+ReLU) backward: a split-K dgrad's reduce
+            also emits that BN's partial-stats slab; an empty slab (unsplit
+            or stride-2 dgrad) takes the partials pass."""
+            if not _FUSEBN_BWD or st_ != 1:
+                dy = ext.conv2d_dgrad(dyo, w, y.shape[2], y.shape[3], st_, pad)
+                return ext.bn_bwd(dy, a, y, g, m, v, True, mk)
+            dy, slab = ext.conv2d_dgrad_bn(dyo, w, y.shape[2], y.shape[3],
+                                           st_, pad, a, y, m, v, True, mk)
+            if slab.numel() > 0:
+                return ext.bn_bwd_pre(dy, slab, a, y, g, m, v, True, mk)
+            return ext.bn_bwd(dy, a, y, g, m, v, True, mk)
+
         dx3, dg3, db3 = ext.bn_bwd(dout, a3, out, g3, m3, v3, True, mk3)
         dw3 = ext.conv2d_wgrad(y2, dx3, 1, 1, 1, 0)
-        dy2 = ext.conv2d_dgrad(dx3, w3, y2.shape[2], y2.shape[3], 1, 0)
-        dx2, dg2, db2 = ext.bn_bwd(dy2, a2, y2, g2, m2, v2, True, mk2)
+        dx2, dg2, db2 = dgrad_bn(dx3, w3, 1, 0, a2, y2, g2, m2, v2, mk2)
         dw2 = ext.conv2d_wgrad(y1, dx2, 3, 3, st, 1)
-        dy1 = ext.conv2d_dgrad(dx2, w2, y1.shape[2], y1.shape[3], st, 1)
-        dx1, dg1, db1 = ext.bn_bwd(dy1, a1, y1, g1, m1, v1, True, mk1)
+        dx1, dg1, db1 = dgrad_bn(dx2, w2, st, 1, a1, y1, g1, m1, v1, mk1)
         dw1 = ext.conv2d_wgrad(x, dx1, 1, 1, 1, 0)
 
         dx0 = ext.conv2d_dgrad(dx1, w1, x.shape[2], x.shape[3], 1, 0)
