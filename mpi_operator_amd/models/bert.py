@@ -30,6 +30,13 @@ import os as _os
 _FUSED_LN = _os.environ.get("MPIAMD_FUSED_LN", "1") == "1"
 
 
+# MPIAMD_FLASH_ATTN (read per call): route seq > 256 and key-masked
+# attention through ops/csrc/flash_attention.hip instead of the eager chain.
+# Default ON: 330 vs 230 seq/s and 6.9 vs 11.6 GiB peak at BERT-Large
+# seq 512 bs 8, same box (profiles/BENCH_HISTORY.md)
+_FLASH_ATTN_DEFAULT = "1"
+
+
 class LayerNorm(nn.Module):
     """LayerNorm with fp32 statistics on the hand-written HIP kernel
     (ops/csrc/layernorm.hip). Default since round 2: the backward's dx
@@ -110,6 +117,16 @@ class SelfAttention(nn.Module):
             # the batched-matmul + softmax chain); emits ctx in [b, s, h]
             # directly — no transpose/reshape passes
             return self.out(Fx.attention(qkv, self.heads, self.scale))
+        if (x.is_cuda and x.dtype == torch.bfloat16 and self.head_dim == 64
+                and (attn_mask is None or attn_mask.shape == (b, 1, 1, s))
+                and _os.environ.get("MPIAMD_FLASH_ATTN",
+                                    _FLASH_ATTN_DEFAULT) != "0"):
+            # tiled online-softmax kernels: s > 256 and/or the additive key
+            # mask BertModel builds; saves a per-row log-sum-exp instead of
+            # [b, nh, s, s] probs. Other mask shapes keep the eager chain.
+            return self.out(Fx.flash_attention(
+                qkv, self.heads, self.scale,
+                attn_mask.reshape(b, s) if attn_mask is not None else None))
         q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # b, nh, s, hd
         scores = torch.matmul(q, k.transpose(-1, -2)) * self.scale
         if attn_mask is not None:

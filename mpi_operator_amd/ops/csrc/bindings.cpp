@@ -108,6 +108,11 @@ hipError_t attn_fwd_launch(const void *, void *, void *, const float *, int,
                            int, int, float, hipStream_t);
 hipError_t attn_bwd_launch(const void *, const void *, const void *, void *,
                            int, int, int, float, hipStream_t);
+hipError_t flash_attn_fwd_launch(const void *, void *, float *, const float *,
+                                 int, int, int, float, hipStream_t);
+hipError_t flash_attn_bwd_launch(const void *, const void *, const void *,
+                                 const float *, float *, const float *, void *,
+                                 int, int, int, float, hipStream_t);
 hipError_t softmax_xent_bwd_launch(const float *, const long *, void *, int,
                                    int, const float *, hipStream_t);
 hipError_t gemm_nt(const void *, const void *, void *, int, int, int, long,
@@ -830,6 +835,71 @@ static Tensor attn_bwd(const Tensor &qkv, const Tensor &dctx,
   return dqkv;
 }
 
+// ------------------- tiled attention (any S, key mask) -------------------
+// qkv: [B, S, 3, H, 64]; returns (ctx [B, S, H*64], lse [B, H, S] fp32).
+// No probs: the backward recomputes P from lse.
+static void flash_check_qkv(const Tensor &qkv, int64_t heads) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 && qkv.size(4) == 64,
+              "qkv must be [B,S,3,H,64]");
+  TORCH_CHECK(qkv.is_contiguous());
+  TORCH_CHECK(qkv.size(3) == heads);
+  TORCH_CHECK(qkv.size(0) >= 1 && qkv.size(1) >= 1);
+}
+
+static Tensor flash_mask(const c10::optional<Tensor> &mask, long B, long S) {
+  Tensor maskc;
+  if (mask.has_value()) {
+    maskc = mask->to(at::kFloat).contiguous();
+    TORCH_CHECK(maskc.is_cuda() && maskc.numel() == B * S,
+                "mask must be [B,S] additive");
+  }
+  return maskc;
+}
+
+static std::vector<Tensor> flash_attn_fwd(const Tensor &qkv, int64_t heads,
+                                          double scale,
+                                          const c10::optional<Tensor> &mask) {
+  flash_check_qkv(qkv, heads);
+  const HIPDeviceGuard guard(qkv.device());
+  int B = qkv.size(0), S = qkv.size(1), H = qkv.size(3);
+  Tensor maskc = flash_mask(mask, B, S);
+  Tensor ctx = at::empty({B, S, (long)H * 64}, qkv.options());
+  Tensor lse = at::empty({B, (long)H, S}, qkv.options().dtype(at::kFloat));
+  CHK(flash_attn_fwd_launch(
+      qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr<float>(),
+      maskc.defined() ? maskc.data_ptr<float>() : nullptr, B, S, H,
+      (float)scale, cur_stream()));
+  return {ctx, lse};
+}
+
+static Tensor flash_attn_bwd(const Tensor &qkv, const Tensor &ctx,
+                             const Tensor &dctx, const Tensor &lse,
+                             double scale,
+                             const c10::optional<Tensor> &mask) {
+  flash_check_qkv(qkv, qkv.dim() == 5 ? qkv.size(3) : 0);
+  const HIPDeviceGuard guard(qkv.device());
+  int B = qkv.size(0), S = qkv.size(1), H = qkv.size(3);
+  TORCH_CHECK(ctx.is_cuda() && ctx.scalar_type() == at::kBFloat16 &&
+              ctx.is_contiguous() && ctx.numel() == (long)B * S * H * 64,
+              "ctx must be [B,S,H*64] bf16");
+  TORCH_CHECK(dctx.is_cuda() && dctx.scalar_type() == at::kBFloat16 &&
+              dctx.numel() == ctx.numel(), "dctx must be [B,S,H*64] bf16");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
+              lse.is_contiguous() && lse.numel() == (long)B * H * S,
+              "lse must be [B,H,S] fp32");
+  Tensor maskc = flash_mask(mask, B, S);
+  Tensor dc = dctx.contiguous();
+  Tensor delta = at::empty_like(lse);
+  Tensor dqkv = at::empty_like(qkv);
+  CHK(flash_attn_bwd_launch(
+      qkv.data_ptr(), ctx.data_ptr(), dc.data_ptr(), lse.data_ptr<float>(),
+      delta.data_ptr<float>(),
+      maskc.defined() ? maskc.data_ptr<float>() : nullptr, dqkv.data_ptr(), B,
+      S, H, (float)scale, cur_stream()));
+  return dqkv;
+}
+
 // ------------------------- fused FFN (GELU) -------------------------
 // fc1 forward with the bias+GELU in the epilogue: returns (g, h_pre)
 static std::vector<Tensor> linear_gelu_fwd(const Tensor &x, const Tensor &w,
@@ -1115,6 +1185,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_gelu_fwd", &linear_gelu_fwd);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("flash_attn_fwd", &flash_attn_fwd);
+  m.def("flash_attn_bwd", &flash_attn_bwd);
   m.def("linear_wgrad_only", &linear_wgrad_only);
   m.def("linear_gelu_dgrad", &linear_gelu_dgrad);
   m.def("masked_xent_bwd", &masked_xent_bwd);

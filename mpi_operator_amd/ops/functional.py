@@ -457,6 +457,47 @@ def attention(qkv, heads, scale, mask=None):
     return AttentionFn.apply(qkv, heads, scale, mask)
 
 
+class FlashAttentionFn(torch.autograd.Function):
+    """Tiled online-softmax MHA (ops/csrc/flash_attention.hip): any sequence
+    length, optional additive key mask [B, S]. Saves qkv, ctx, the per-row
+    log-sum-exp [B, H, S] and the mask — no [B, H, S, S] probs; the backward
+    recomputes P from lse (deterministic, no atomics).
+    qkv: [B, S, 3, H, 64] → ctx [B, S, H·64]."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, scale, mask):
+        qkv = qkv.contiguous()
+        if qkv.is_cuda and qkv.dtype == torch.bfloat16:
+            out, lse = hip_ext().flash_attn_fwd(qkv, heads, scale, mask)
+        else:
+            out, lse = ref.flash_attention_fwd(qkv, heads, scale, mask)
+        ctx.save_for_backward(qkv, out, lse, mask)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, mask = ctx.saved_tensors
+        if qkv.is_cuda and qkv.dtype == torch.bfloat16:
+            dqkv = hip_ext().flash_attn_bwd(qkv, out, dout.contiguous(), lse,
+                                            ctx.scale, mask)
+        else:
+            dqkv = ref.flash_attention_bwd(qkv, out, dout, lse, ctx.scale,
+                                           mask)
+        return dqkv, None, None, None
+
+
+def flash_attention(qkv, heads, scale, mask=None):
+    """softmax(Q·Kᵀ·scale + mask)·V for qkv [B, S, 3, H, 64] → [B, S, H·64].
+
+    mask: optional additive key mask [B, S] (0 = keep, a large negative
+    such as finfo(float32).min = drop), shared by all heads and query rows.
+    CUDA bf16 runs the HIP kernels; anything else the fp32 reference.
+    A batch row with NO valid key is outside the contract: its output and
+    gradients are only guaranteed to be finite."""
+    return FlashAttentionFn.apply(qkv, heads, scale, mask)
+
+
 class BertLayerFn(torch.autograd.Function):
     """One whole transformer encoder layer (fused QKV → attention →
     out-proj → LN-join → FFN(GELU) → LN-join) as a single autograd node,

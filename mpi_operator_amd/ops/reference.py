@@ -155,3 +155,45 @@ def dgelu(x):
     u = c * (xf + 0.044715 * xf ** 3)
     t = torch.tanh(u)
     return 0.5 * (1 + t) + 0.5 * xf * (1 - t * t) * c * (1 + 3 * 0.044715 * xf * xf)
+
+
+def _flash_scores(qkv, scale: float, mask):
+    """fp32 scaled, masked scores [B,H,S,S] plus q, k, v as [B,H,S,D]."""
+    q, k, v = (qkv[:, :, i].transpose(1, 2).float() for i in range(3))
+    s = torch.matmul(q, k.transpose(-1, -2)) * scale
+    if mask is not None:
+        s = s + mask.float().reshape(qkv.shape[0], 1, 1, qkv.shape[1])
+    return s, q, k, v
+
+
+def flash_attention_fwd(qkv, heads: int, scale: float, mask=None):
+    """Specification of flash_attn_fwd_k. qkv [B,S,3,H,D], mask [B,S]
+    additive or None → (ctx [B,S,H·D] in qkv's dtype, lse [B,H,S] fp32).
+    Keeps the per-row log-sum-exp, not the probabilities."""
+    B, S, _, H, D = qkv.shape
+    assert H == heads
+    s, _, _, v = _flash_scores(qkv, scale, mask)
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.unsqueeze(-1))
+    ctx = torch.matmul(p, v).transpose(1, 2).reshape(B, S, H * D)
+    return ctx.to(qkv.dtype), lse
+
+
+def flash_attention_bwd(qkv, ctx, dctx, lse, scale: float, mask=None):
+    """Specification of the flash backward kernels: P is recomputed from
+    lse and the softmax-gradient row term is delta = rowsum(dctx∘ctx);
+    no saved probabilities. Returns dqkv [B,S,3,H,D]."""
+    B, S, _, H, D = qkv.shape
+    s, q, k, v = _flash_scores(qkv, scale, mask)
+    p = torch.exp(s - lse.float().unsqueeze(-1))
+    do = dctx.reshape(B, S, H, D).transpose(1, 2).float()
+    o = ctx.reshape(B, S, H, D).transpose(1, 2).float()
+    delta = (do * o).sum(-1, keepdim=True)
+    dp = torch.matmul(do, v.transpose(-1, -2))
+    ds = (dp - delta) * p * scale
+    dv = torch.matmul(p.transpose(-1, -2), do)
+    dq = torch.matmul(ds, k)
+    dk = torch.matmul(ds.transpose(-1, -2), q)
+    dqkv = torch.stack(
+        [dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2)], dim=2)
+    return dqkv.to(qkv.dtype)
