@@ -544,14 +544,26 @@ static void bn_geom(long M, int C8, int &grid, int &rows_per_block) {
   grid = (int)(g > cap ? cap : (g < 1 ? 1 : g));
 }
 
-static int bn_apply_grid(long M, int C8) {
-  // cap 2048 measured best (3846-3854 vs 3833-3834 img/s at 4096, 3800
-  // at 8192, four-sample same-box sweep); MPIAMD_BN_APPLY_GRID overrides
+// cap 2048 measured best (3846-3854 vs 3833-3834 img/s at 4096, 3800
+// at 8192, four-sample same-box sweep); MPIAMD_BN_APPLY_GRID overrides
+static long bn_apply_grid_cap() {
   static const long cap = [] {
     const char *e = getenv("MPIAMD_BN_APPLY_GRID");
     long v = e ? atol(e) : 0;
     return (v >= 64 && v <= 16384) ? v : 2048L;
   }();
+  return cap;
+}
+
+// route introspection (host only): [bn_grid, bn_apply_grid] caps as the
+// launchers in this TU resolve them
+extern "C" void bn_route_knobs(int *out) {
+  out[0] = bn_grid_cap(1);
+  out[1] = (int)bn_apply_grid_cap();
+}
+
+static int bn_apply_grid(long M, int C8) {
+  const long cap = bn_apply_grid_cap();
   int rpb = 256 / C8;
   long g = (M + rpb - 1) / rpb;
   return (int)(g > cap ? cap : (g < 1 ? 1 : g));

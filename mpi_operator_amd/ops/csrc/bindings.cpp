@@ -16,11 +16,29 @@ using at::Tensor;
 // Late-stage convs produce few 128x128 output tiles (7x7 spatial ~100
 // blocks on 256 CUs): split the reduce dim so fwd/dgrad fill the chip,
 // paying one fp32 slab + reduce pass.
-int conv_splits(long M, int Ncols, int K) {
+// MPIAMD_CONV_SPLITS=n (n >= 1) forces the conv fwd/dgrad split count;
+// -1 = the heuristic below.
+int conv_splits_force() {
   static const int force = [] {
     const char *e = getenv("MPIAMD_CONV_SPLITS");
     return e ? atoi(e) : -1;
   }();
+  return force >= 1 ? force : -1;
+}
+
+// target-block budget of the conv-wgrad split count (conv2d_wgrad);
+// MPIAMD_WGRAD_BUDGET overrides within [64, 2048] for A/B (default 512)
+int wgrad_budget() {
+  static const int budget = [] {
+    const char *e = getenv("MPIAMD_WGRAD_BUDGET");
+    int v = e ? atoi(e) : 0;
+    return (v >= 64 && v <= 2048) ? v : 512;
+  }();
+  return budget;
+}
+
+int conv_splits(long M, int Ncols, int K) {
+  const int force = conv_splits_force();
   if (force >= 1) return force;
   long tiles = ((M + 127) / 128) * ((Ncols + 127) / 128);
   int nk = (K + 63) / 64;
@@ -59,6 +77,12 @@ Tensor empty_cl_bf16(int64_t n, int64_t c, int64_t h, int64_t w, const Tensor &l
 
 // ---- extern "C" launchers from the .hip TUs ----
 extern "C" {
+// route introspection: each TU reports the knobs its own launchers resolve
+void gemm_route_knobs(int *);  // gemm.hip, 15 values
+int gemm_nt_route_id(int, int, int, int);
+void conv_route_knobs(int *);  // conv.hip, 3 values
+void ln_route_knobs(int *);    // layernorm.hip, 2 values
+void bn_route_knobs(int *);    // batchnorm.hip, 2 values
 hipError_t add_relu_fwd(const void *, const void *, void *, long, hipStream_t);
 hipError_t add_bf16(const void *, const void *, void *, long, hipStream_t);
 hipError_t add_relu_bwd(const void *, const void *, void *, long, hipStream_t);
@@ -257,11 +281,7 @@ static Tensor conv2d_wgrad(const Tensor &x, const Tensor &dy, int64_t R,
   // target-block budget was tuned on the 4-wave pipeline (2 WG/CU); the
   // 8-wave kernel fills at half the workgroups — MPIAMD_WGRAD_BUDGET
   // overrides for A/B (default 512)
-  static const int budget = [] {
-    const char *e = getenv("MPIAMD_WGRAD_BUDGET");
-    int v = e ? atoi(e) : 0;
-    return (v >= 64 && v <= 2048) ? v : 512;
-  }();
+  const int budget = wgrad_budget();
   int splits = std::max(budget / tiles, 1);
   splits = std::min(splits, std::max(nk / 8, 1));
   splits = std::min(splits, 256);
@@ -1152,7 +1172,60 @@ static Tensor gemm_nt_b(const Tensor &a, const Tensor &b, bool c_f32) {
   return c;
 }
 
+// ------------------- route introspection (host only) -------------------
+// Resolved value of every C++ MPIAMD_* knob, reported by the TU whose
+// launchers read it (never a second getenv here). Touches no device.
+static py::dict route_info() {
+  int g[15], c[3], l[2], b[2];
+  gemm_route_knobs(g);
+  conv_route_knobs(c);
+  ln_route_knobs(l);
+  bn_route_knobs(b);
+  py::dict d;
+  d["pipemix"] = g[0] != 0;
+  d["pipe8"] = g[1] != 0;
+  d["p256x16"] = g[2] != 0;
+  d["gemm256"] = g[3] != 0;
+  d["pipe"] = g[4] != 0;
+  d["pipent"] = g[5] != 0;
+  d["glds"] = g[6] != 0;
+  d["onebuf"] = g[7] != 0;
+  d["splitmajor"] = g[8] != 0;
+  d["sk_cpx"] = g[9] != 0;
+  d["fwd_sk"] = g[10] != 0;
+  d["dx_sk"] = g[11]; // -1 shape-aware default, 0 never, 1 always
+  d["linear_sk"] = g[12] != 0;
+  d["gelu_deriv"] = g[13] != 0;
+  d["gelubwd_wt"] = g[14] != 0;
+  d["pipegather"] = c[0] != 0;
+  d["pipegather_wgrad"] = c[1] != 0;
+  d["pipes2"] = c[2] != 0;
+  d["ln_spec"] = l[0] != 0;
+  d["ln2"] = l[1] != 0;
+  d["bn_grid"] = b[0];
+  d["bn_apply_grid"] = b[1];
+  d["conv_splits_force"] = conv_splits_force(); // -1 = heuristic
+  d["wgrad_budget"] = wgrad_budget();
+  return d;
+}
+
+static const char *nt_route(int M, int N, int K, int splits) {
+  static const char *const names[] = {"pipe256", "nt256", "pipemix", "glds",
+                                      "reg"};
+  int r = gemm_nt_route_id(M, N, K, splits);
+  TORCH_CHECK(r >= 0 && r < 5, "unknown NT route id ", r);
+  return names[r];
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("route_info", &route_info);
+  m.def("nt_route", &nt_route, py::arg("M"), py::arg("N"), py::arg("K"),
+        py::arg("splits") = 1);
+  // does the fc2-dx GEMM of dy [M][K] · w2 [K][N] take the transpose-plus-
+  // pipe256 route (MPIAMD_GELUBWD_WT)? The route's own predicate.
+  m.def("gelubwd_wt_route", [](int M, int N, int K) {
+    return gemm_gelubwd_wants_wt(M, N, K) != 0;
+  });
   m.def("conv2d_fwd", &conv2d_fwd);
   m.def("conv2d_dgrad", &conv2d_dgrad);
   m.def("conv2d_fwd_bn", &conv2d_fwd_bn, py::arg("x"), py::arg("w"),

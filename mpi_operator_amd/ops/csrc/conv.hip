@@ -478,12 +478,8 @@ static hipError_t conv_dgrad_s2(const void *dy, const void *w, void *dx,
       lb.w = (const uint16_t *)w;
       lb.C = C; lb.Q = Kout; lb.K = K; lb.RSC = R * S * C; lb.S = S;
       lb.nth = sa.nth; lb.ntw = sa.ntw;
-      static const bool pipes2 = [] { // MPIAMD_PIPES2=0: A/B lever
-        const char *env = getenv("MPIAMD_PIPES2");
-        return !(env && env[0] == '0');
-      }();
       hipError_t e;
-      if (use_pipegather() && pipes2) {
+      if (use_pipes2()) {
         // pipe route (8-wave under MPIAMD_PIPE8): same parity GEMM with
         // the glds/tr staging; Stride2*Writer epilogues are pipe-generic
         NtPipe<DgradS2Src> sa2{{(const uint16_t *)dy, HO, WO, Kout, W2, H2,
@@ -765,4 +761,13 @@ extern "C" hipError_t conv_wgrad_implicit(const void *dy, const void *x,
   }
   if (e != hipSuccess) return e;
   return splitk_reduce(partial, splits, (long)Kout * RSC, dw, dw_bf16, strm);
+}
+
+// ---- route introspection (host only; tests/test_knob_routes.py) ----------
+// The gather gates as THIS TU's conv launchers resolve them: fwd/dgrad
+// gather, wgrad gather, stride-2 dgrad parity GEMMs.
+extern "C" void conv_route_knobs(int *out) {
+  out[0] = use_pipegather();
+  out[1] = use_pipegather_wgrad();
+  out[2] = use_pipes2();
 }

@@ -43,12 +43,15 @@ extern "C" hipError_t gemm_nt_bias(const void *a, const void *b,
 // bs32 (1372 -> 1381): default ON, MPIAMD_FWD_SK=0 disables. Heuristic
 // shared with the dw path.
 extern "C" int gemm_tn_tn_splits(int M, int N, int K); // below
-extern "C" int gemm_fwd_splits(int M, int N, int K) {
+static bool fwd_sk_on() {
   static const bool on = [] {
     const char *e = getenv("MPIAMD_FWD_SK");
     return !(e && e[0] == '0');
   }();
-  if (!on || N % 8) return 1;
+  return on;
+}
+extern "C" int gemm_fwd_splits(int M, int N, int K) {
+  if (!fwd_sk_on() || N % 8) return 1;
   int sp = gemm_tn_tn_splits(M, N, K);
   return sp > 4 ? 4 : sp;
 }
@@ -114,6 +117,25 @@ extern "C" hipError_t gemm_nt_gelu_bias(const void *x, const void *w,
 extern "C" hipError_t transpose2d_bf16(const void *, void *, int, int, long,
                                        hipStream_t); // defined below
 
+static bool gelubwd_wt_on() {
+  static const bool on = [] {
+    const char *e = getenv("MPIAMD_GELUBWD_WT");
+    return e && e[0] == '1';
+  }();
+  return on;
+}
+
+// fc2-dx takes the transpose-plus-pipe256 route (below) iff this holds:
+// knob on, full 256² tiles above the occupancy floor, dense C, and a dense
+// w2 [K][N] (ldb == N — transpose2d_bf16 reads rows of exactly N). The one
+// predicate serves the caller's scratch allocation (gemm_gelubwd_wants_wt)
+// and the route. It used to test ldb == K, which only a square w2 meets:
+// at every FFN shape the knob silently kept the TN route.
+static bool gelubwd_takes_wt(int M, int N, int K, long ldb, long ldc) {
+  return gelubwd_wt_on() && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 &&
+         ldc == N && ldb == N && (long)(M / 256) * (N / 256) >= 128;
+}
+
 // FFN backward: dh = (dy·w2) ⊙ gelu'(h) — the fc2-dx GEMM multiplying by
 // the SAVED derivative in the epilogue (GeluBwdWriter); A NT, B (w2) TN.
 template <class WR>
@@ -125,8 +147,7 @@ static hipError_t gelubwd_route(WR wrt, const void *dy, const void *w,
   // TN-staged pipe_mix but 550+ TF on the NT pipe256 — worth materializing
   // w2^T once per call (~8 us for 33 MB) to take the NT route. wt_buf is
   // caller-allocated [N][K] bf16.
-  if (wt_buf && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && ldc == N &&
-      ldb == K && (long)(M / 256) * (N / 256) >= 128) {
+  if (wt_buf && gelubwd_takes_wt(M, N, K, ldb, ldc)) {
     hipError_t e = transpose2d_bf16(w, wt_buf, K, N, K, s);
     if (e != hipSuccess) return e;
     GemmLoader la{(const uint16_t *)dy, M, lda, K};
@@ -149,12 +170,7 @@ static hipError_t gelubwd_route(WR wrt, const void *dy, const void *w,
 // per-kernel mix-vs-256 gap in prof10 — pipe256 with the deriv-reading
 // epilogue loses its edge. Default OFF (MPIAMD_GELUBWD_WT=1 enables).
 extern "C" int gemm_gelubwd_wants_wt(int M, int N, int K) {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_GELUBWD_WT");
-    return e && e[0] == '1';
-  }();
-  return on && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 &&
-         (long)(M / 256) * (N / 256) >= 128;
+  return gelubwd_takes_wt(M, N, K, N, N);
 }
 
 extern "C" hipError_t gemm_nt_tn_gelubwd(const void *dy, const void *w,
@@ -217,11 +233,15 @@ extern "C" int gemm_tn_tn_splits(int M, int N, int K); // defined below
 // need it badly (bs8's 64-wg dx: 690 with splits vs 614 without; so does
 // bert-base's 192-wg grid). Split only when tiles < 256.
 // MPIAMD_DX_SK: 0 = never split, 1 = always use the dw heuristic.
-extern "C" int gemm_nt_tn_splits(int M, int N, int K) {
+static int dx_sk_mode() { // -1 = shape-aware default
   static const int mode = [] {
     const char *e = getenv("MPIAMD_DX_SK");
     return e ? (e[0] == '1' ? 1 : 0) : -1;
   }();
+  return mode;
+}
+extern "C" int gemm_nt_tn_splits(int M, int N, int K) {
+  const int mode = dx_sk_mode();
   if (mode == 0) return 1;
   long tiles = ((M + 127) / 128) * ((N + 127) / 128);
   if (mode != 1 && tiles >= 256) return 1;
@@ -276,11 +296,15 @@ extern "C" hipError_t gemm_tn_tn(const void *a, const void *b, void *c, int M,
 // underfills the chip (BERT attn-out dw = 64 workgroups on 256 CUs with a
 // K of batch*seq): fp32 slabs in `partial` [splits][M*ldc] reduced into a
 // dense fp32 C. Caller sizes `partial` with `splits` from gemm_tn_tn_splits.
-extern "C" int gemm_tn_tn_splits(int M, int N, int K) {
-  static const bool off = [] {
+static bool linear_sk_on() {
+  static const bool on = [] {
     const char *e = getenv("MPIAMD_LINEAR_SK");
-    return e && e[0] == '0';
+    return !(e && e[0] == '0');
   }();
+  return on;
+}
+extern "C" int gemm_tn_tn_splits(int M, int N, int K) {
+  const bool off = !linear_sk_on();
   long tiles = ((M + 127) / 128) * ((N + 127) / 128);
   int nk = (K + 63) / 64;
   // nk>=32: at bs=8-class shapes (nk=16) the slab+reduce overhead beats
@@ -390,4 +414,32 @@ extern "C" hipError_t mfma_probe(const void *a, const void *b, float *d,
                                  hipStream_t s) {
   mfma_probe_k<<<1, 64, 0, s>>>((const uint16_t *)a, (const uint16_t *)b, d);
   return hipGetLastError();
+}
+
+// ---- route introspection (host only; tests/test_knob_routes.py) ----------
+// Each value is what this TU's launchers resolve — the same helpers, the
+// same per-process statics — so a test can prove a knob selected the route
+// it names. Order is the contract with bindings.cpp route_info().
+extern "C" void gemm_route_knobs(int *out) {
+  out[0] = use_pipemix();
+  out[1] = use_pipe8();
+  out[2] = use_p256x16();
+  out[3] = use_gemm256();
+  out[4] = use_pipe();
+  out[5] = use_pipent();
+  out[6] = use_glds();
+  out[7] = use_onebuf();
+  out[8] = use_splitmajor();
+  out[9] = use_sk_cpx();
+  out[10] = fwd_sk_on();
+  out[11] = dx_sk_mode();
+  out[12] = linear_sk_on();
+  out[13] = gelu_deriv_mode();
+  out[14] = gelubwd_wt_on();
+}
+
+// nt_gemm_route for a dense NT problem (kdim == K on both operands,
+// ldc == N): 0 pipe256, 1 nt256, 2 pipemix, 3 glds, 4 reg.
+extern "C" int gemm_nt_route_id(int M, int N, int K, int splits) {
+  return (int)nt_gemm_route(M, N, K, N, K, K, splits);
 }

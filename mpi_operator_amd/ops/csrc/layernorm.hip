@@ -344,6 +344,23 @@ static bool ln_spec() {
   return on;
 }
 
+// MPIAMD_LN2=1: 2-row-interleaved dx kernel (ln_bwd_dx2_k) for N <= 1024
+// (A/B lever). Default OFF.
+static bool ln2_mode() {
+  static const bool on = [] {
+    const char *e = getenv("MPIAMD_LN2");
+    return e && e[0] == '1';
+  }();
+  return on;
+}
+
+// route introspection (host only): [ln_spec, ln2] as the launchers below
+// resolve them
+extern "C" void ln_route_knobs(int *out) {
+  out[0] = ln_spec();
+  out[1] = ln2_mode();
+}
+
 static int ln_grid(long M, int waves) {
   long g = (M + waves - 1) / waves;
   if (g > 1024) g = 1024;
@@ -406,11 +423,7 @@ extern "C" hipError_t ln_bwd(const void *dy, const void *x, const float *gamma,
                              int N, int *grid_out, hipStream_t s) {
   if (N % 8 || N > 2048) return hipErrorInvalidValue;
   int C8 = N / 8;
-  static const bool ln2 = [] { // MPIAMD_LN2: 2-row-interleaved dx (A/B)
-    const char *e = getenv("MPIAMD_LN2");
-    return e && e[0] == '1';
-  }();
-  if (ln2 && N <= 1024) {
+  if (ln2_mode() && N <= 1024) {
     long waves2 = (M + 1) / 2;
     int grid2 = (int)((waves2 + 3) / 4);
     if (grid2 > 1024) grid2 = 1024;

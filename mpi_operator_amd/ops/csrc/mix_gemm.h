@@ -555,6 +555,28 @@ __global__ __launch_bounds__(NT_THREADS) void mix_gemm_k(
 #undef MXG_A
 #undef MXG_B
 
+// MPIAMD_SPLITMAJOR=1: split-major dispatch of the mix split-K grid.
+// default OFF: the standalone-harness win (+16-28% on synthetic TnTn
+// wgrad shapes) did not transfer to the full model (-0.4% same-box on the
+// bench) — real wgrads gather B via XcolStage and use smaller splits
+static inline bool use_splitmajor() {
+  static const bool on = [] {
+    const char *e = getenv("MPIAMD_SPLITMAJOR");
+    return e && e[0] == '1';
+  }();
+  return on;
+}
+
+// MPIAMD_GEMM_ONEBUF=1: single-LDS-buffer mix tile (register-staged
+// operands only, see launch_mix_gemm_wr). Default OFF.
+static inline bool use_onebuf() {
+  static const bool on = [] {
+    const char *e = getenv("MPIAMD_GEMM_ONEBUF");
+    return e && e[0] == '1';
+  }();
+  return on;
+}
+
 template <class SA, class SB, class WR>
 static hipError_t launch_mix_gemm_wr(const SA &sa, const SB &sb, void *c,
                                      int M, int N, int K, const WR &wrt,
@@ -569,23 +591,12 @@ static hipError_t launch_mix_gemm_wr(const SA &sa, const SB &sb, void *c,
   // T1 XCD swizzle: give each XCD a contiguous chunk of tiles so neighbor
   // tiles (sharing operand panels) hit the same per-XCD L2. Needs nwg%8==0
   // and enough tiles to matter.
-  // default OFF: the standalone-harness win (+16-28% on synthetic TnTn
-  // wgrad shapes) did not transfer to the full model (-0.4% same-box on the
-  // bench) — real wgrads gather B via XcolStage and use smaller splits
-  static const int swap_env = [] {
-    const char *e = getenv("MPIAMD_SPLITMAJOR");
-    return e && e[0] == '1' ? 1 : 0;
-  }();
-  int swap = (splits > 1 && splits % 8 == 0) ? swap_env : 0;
+  int swap = (splits > 1 && splits % 8 == 0 && use_splitmajor()) ? 1 : 0;
   int cpx = (nwg % 8 == 0 && nwg >= 32 && (splits == 1 || swap)) ? nwg / 8 : 0;
   dim3 grid = swap ? dim3(splits, nwg) : dim3(nwg, splits);
-  static const bool onebuf_env = [] {
-    const char *e = getenv("MPIAMD_GEMM_ONEBUF");
-    return e && e[0] == '1';
-  }();
   // glds targets the next buffer while the current one is being read — a
   // single buffer would race
-  const bool onebuf = onebuf_env && !SA::GLDS && !SB::GLDS;
+  const bool onebuf = use_onebuf() && !SA::GLDS && !SB::GLDS;
   if (onebuf) {
     if (c_f32)
       mix_gemm_k<SA, SB, true, WR, true><<<grid, NT_THREADS, 0, s>>>(
@@ -624,39 +635,59 @@ static hipError_t launch_mix_gemm(const SA &sa, const SB &sb, void *c, int M,
 // forward (conv.hip conv_fwd_bn) runs exactly the kernel the unfused conv
 // runs for the same shape and environment.
 enum NtRoute { NT_PIPE256, NT_256, NT_PIPEMIX, NT_GLDS, NT_REG };
-static inline NtRoute nt_gemm_route(int M, int N, int K, long ldc, int kdim_a,
-                                    int kdim_b, int splits) {
-  static const bool use_256 = [] {
+
+// MPIAMD_GEMM256=0: no 256²-tile family (128² everywhere).
+static inline bool use_gemm256() {
+  static const bool on = [] {
     const char *e = getenv("MPIAMD_GEMM256");
     return !(e && e[0] == '0');
   }();
+  return on;
+}
+
+// 4-phase deep pipeline (pipe256.h) for K%64 full-tile shapes;
+// MPIAMD_PIPE=0 reverts to the round-1 BK=32 3-buffer kernel (gemm256.h)
+static inline bool use_pipe() {
+  static const bool on = [] {
+    const char *e = getenv("MPIAMD_PIPE");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
+// MPIAMD_PIPENT=0 reverts just the NT 128² pipe fallback (bisect lever).
+static inline bool use_pipent() {
+  static const bool on = [] {
+    const char *e = getenv("MPIAMD_PIPENT");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
+// MPIAMD_GLDS=0: register-staged loads instead of global_load_lds in the
+// mix tile.
+static inline bool use_glds() {
+  static const bool on = [] {
+    const char *e = getenv("MPIAMD_GLDS");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
+static inline NtRoute nt_gemm_route(int M, int N, int K, long ldc, int kdim_a,
+                                    int kdim_b, int splits) {
   // occupancy floor: 256² tiles run 1 block/CU (96 KB LDS), so a grid
   // under ~half the 256 CUs loses more to idle CUs than the pipeline wins
   // (measured: M=12544,N=512 → 98 wgs: 338 vs 506 TF on the 128² path;
   // M=50176,N=256 → 196 wgs: 505 vs 417 — the crossover is between)
-  // 4-phase deep pipeline (pipe256.h) for K%64 full-tile shapes;
-  // MPIAMD_PIPE=0 reverts to the round-1 BK=32 3-buffer kernel (gemm256.h)
-  static const bool use_pipe = [] {
-    const char *e = getenv("MPIAMD_PIPE");
-    return !(e && e[0] == '0');
-  }();
-  if (use_256 && splits <= 1 && M % 256 == 0 && N % 256 == 0 && K % 32 == 0 &&
-      K > 0 && kdim_a == K && kdim_b == K && ldc == N &&
+  if (use_gemm256() && splits <= 1 && M % 256 == 0 && N % 256 == 0 &&
+      K % 32 == 0 && K > 0 && kdim_a == K && kdim_b == K && ldc == N &&
       (long)(M / 256) * (N / 256) >= 128)
-    return (use_pipe && K % 64 == 0) ? NT_PIPE256 : NT_256;
+    return (use_pipe() && K % 64 == 0) ? NT_PIPE256 : NT_256;
   // non-full-tile / small-grid shapes: the 128²-tile deep pipeline
   // (pipe_mix.h) — ragged edges handled by its zeros-page staging.
-  // MPIAMD_PIPENT=0 reverts just this NT fallback (bisect lever).
-  static const bool use_pipent = [] {
-    const char *e = getenv("MPIAMD_PIPENT");
-    return !(e && e[0] == '0');
-  }();
-  if (use_pipemix() && use_pipent) return NT_PIPEMIX;
-  static const bool use_glds = [] {
-    const char *e = getenv("MPIAMD_GLDS");
-    return !(e && e[0] == '0');
-  }();
-  return use_glds ? NT_GLDS : NT_REG;
+  if (use_pipemix() && use_pipent()) return NT_PIPEMIX;
+  return use_glds() ? NT_GLDS : NT_REG;
 }
 
 template <class LA, class LB>

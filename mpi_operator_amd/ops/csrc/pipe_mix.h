@@ -79,13 +79,41 @@ static inline bool use_pipegather() {
 // wgrad-only override: the -2.9% PIPEGATHER measurement bundled fwd/dgrad
 // and wgrad gathers; A/B'd alone the Xcol wgrad pipe WINS (3566 -> 3573
 // img/s ResNet101, 6129 ResNet50 same-box) — default ON.
-// MPIAMD_PIPEGATHER_WGRAD=0 reverts to the register-staged mix gather.
+// The three gates nest: MPIAMD_PIPEMIX=0 reverts everything,
+// MPIAMD_PIPEGATHER=0 reverts the fwd, dgrad AND wgrad gathers, and
+// MPIAMD_PIPEGATHER_WGRAD=0 reverts the wgrad gather alone to the
+// register-staged mix gather. (Until PIPEGATHER defaulted on this was
+// `(pipemix && wgrad) || pipegather`, which made WGRAD=0 a no-op and left
+// wgrad on the pipe under PIPEGATHER=0.)
 static inline bool use_pipegather_wgrad() {
   static const bool on = [] {
     const char *e = getenv("MPIAMD_PIPEGATHER_WGRAD");
     return !(e && e[0] == '0');
   }();
-  return (use_pipemix() && on) || use_pipegather();
+  return use_pipegather() && on;
+}
+
+// Stride-2 dgrad parity GEMMs on the pipe (conv.hip conv_dgrad_s2);
+// MPIAMD_PIPES2=0 keeps them on DgradS2Stage while every other gather
+// stays on the pipe (A/B lever).
+static inline bool use_pipes2() {
+  static const bool on = [] {
+    const char *e = getenv("MPIAMD_PIPES2");
+    return !(e && e[0] == '0');
+  }();
+  return use_pipegather() && on;
+}
+
+// XCD fold also applies under split-K: the 2-D grid dispatches x-fastest,
+// so within each split slice consecutive tile ids still round-robin the
+// XCDs and the fold restores contiguous tile bands per XCD L2.
+// MPIAMD_SK_CPX=0 restores the old splits==1-only gate for A/B.
+static inline bool use_sk_cpx() {
+  static const bool on = [] {
+    const char *e = getenv("MPIAMD_SK_CPX");
+    return !(e && e[0] == '0');
+  }();
+  return on;
 }
 
 // ---- SrcMaps ----------------------------------------------------------
@@ -655,15 +683,7 @@ static hipError_t launch_pipe_mix_wr(const SA &sa, const SB &sb, void *c,
   int kts = (nk + splits - 1) / splits;
   long split_stride = (long)M * ldc;
   int nwg = tiles_m * tiles_n;
-  // XCD fold also applies under split-K: the 2-D grid dispatches x-fastest,
-  // so within each split slice consecutive tile ids still round-robin the
-  // XCDs and the fold restores contiguous tile bands per XCD L2.
-  // MPIAMD_SK_CPX=0 restores the old splits==1-only gate for A/B.
-  static const bool sk_cpx = [] {
-    const char *e = getenv("MPIAMD_SK_CPX");
-    return !(e && e[0] == '0');
-  }();
-  int cpx = (nwg % 8 == 0 && nwg >= 32 && (splits == 1 || sk_cpx))
+  int cpx = (nwg % 8 == 0 && nwg >= 32 && (splits == 1 || use_sk_cpx()))
                 ? nwg / 8 : 0;
   dim3 grid(nwg, splits);
   if (c_f32)
@@ -880,7 +900,10 @@ static hipError_t launch_pipe_mix8_wr(const SA8 &sa, const SB8 &sb, void *c,
   int kts = (nk + splits - 1) / splits;
   long split_stride = (long)M * ldc;
   int nwg = tiles_m * tiles_n;
-  int cpx = (nwg % 8 == 0 && nwg >= 32) ? nwg / 8 : 0;
+  // same MPIAMD_SK_CPX gate as the 4-wave launcher (the 8-wave copy had
+  // dropped it, so the knob did nothing under the default MPIAMD_PIPE8)
+  int cpx = (nwg % 8 == 0 && nwg >= 32 && (splits == 1 || use_sk_cpx()))
+                ? nwg / 8 : 0;
   dim3 grid(nwg, splits);
   if (c_f32)
     pipe_mix8_k<SA8, SB8, true, WR><<<grid, 512, 0, s>>>(

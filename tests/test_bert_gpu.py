@@ -24,15 +24,24 @@ def test_bert_linear_gpu_matches_fp32():
 
 @pytest.mark.parametrize("M,N,K", [(512, 1000, 2048), (96, 24, 40), (256, 3072, 768),
                                    (8192, 256, 512),  # split-K dw (16 slabs)
-                                   (4096, 1024, 1024)])  # attn-out shape (8 slabs)
+                                   (4096, 1024, 1024),  # attn-out shape (8 slabs)
+                                   # out_features not %8 (zero-padded dy in
+                                   # linear_bwd, ragged TN column granules):
+                                   (32, 2, 768),    # NSP head
+                                   (64, 10, 64),    # SimpleCNN classifier
+                                   (96, 30, 40)])   # the vocab-30522 class
 def test_linear_bwd_ragged_shapes(M, N, K):
-    """dx/dw via the TN-staged kernels on shapes incl. non-%128, non-%8."""
+    """dx/dw via the TN-staged kernels on shapes incl. non-%128, non-%8,
+    and linear_fwd at the same shapes."""
     from mpi_operator_amd.ops import hip_ext
     ext = hip_ext()
     torch.manual_seed(1)
     x = ((torch.rand(M, K, device="cuda") * 2 - 1)).to(torch.bfloat16)
     w = ((torch.rand(N, K, device="cuda") * 2 - 1) * 0.05).to(torch.bfloat16)
     dy = ((torch.rand(M, N, device="cuda") * 2 - 1)).to(torch.bfloat16)
+    b = torch.randn(N, device="cuda")
+    y = ext.linear_fwd(x, w, b)
+    assert relerr(y, x.float() @ w.float().t() + b) < 0.02
     dx, dw, db = ext.linear_bwd(dy, x, w)
     assert relerr(dx, dy.float() @ w.float()) < 0.02
     assert relerr(dw, dy.float().t() @ x.float()) < 0.02
@@ -93,7 +102,10 @@ def test_mlm_head_loss_matches_composed_path():
         assert num / den < 0.02, (num / den, a.shape)
 
 
-@pytest.mark.parametrize("M,N", [(4096, 1024), (100, 768), (7, 2048)])
+@pytest.mark.parametrize("M,N", [(4096, 1024), (100, 768), (7, 2048),
+                                 # odd M at N <= 1024: the last row pair of the
+                                 # 2-row dx kernel (MPIAMD_LN2) has no partner
+                                 (5, 1024)])
 def test_layernorm_fwd_bwd_matches_fp32(M, N):
     from mpi_operator_amd.ops import functional as Fx
     torch.manual_seed(3)
@@ -140,6 +152,34 @@ def test_masked_xent_matches_fp32_reference():
     err = (lg.grad.float() - lf.grad).abs().max().item()
     scale = lf.grad.abs().max().item()
     assert err < 0.05 * scale + 1e-6, (err, scale)
+
+
+@pytest.mark.parametrize("V", [1001, 1002])
+def test_masked_xent_small_ragged_vocab(V):
+    """Rows 0-3 start at four different 16-byte phases (row pitch 2002 or
+    2004 bytes), so the scalar head takes both even and odd lengths, and
+    most of the 256 threads own no vector octet. Targets hit the first
+    column (in the head or the first octet) and the last (in the tail).
+    Bounds of test_masked_xent_matches_fp32_reference."""
+    from mpi_operator_amd.ops import functional as Fx
+    torch.manual_seed(4)
+    B = 8
+    logits = (torch.randn(B, V, device="cuda") * 2).to(torch.bfloat16)
+    target = torch.randint(0, V, (B,), device="cuda")
+    target[0], target[1], target[2] = 0, V - 1, -100
+    lg = logits.clone().requires_grad_(True)
+    loss = Fx.masked_softmax_cross_entropy(lg, target)
+    loss.backward()
+    lf = logits.float().clone().requires_grad_(True)
+    ref_loss = torch.nn.functional.cross_entropy(lf, target, ignore_index=-100)
+    ref_loss.backward()
+    print("loss", loss.item(), "ref", ref_loss.item())
+    assert abs(loss.item() - ref_loss.item()) < 2e-2 * abs(ref_loss.item()) + 1e-3
+    err = (lg.grad.float() - lf.grad).abs().max().item()
+    scale = lf.grad.abs().max().item()
+    print("dlogits err", err, "scale", scale)
+    assert err < 0.05 * scale + 1e-6, (err, scale)
+    assert lg.grad[2].abs().max().item() == 0.0  # the ignored row
 
 
 def test_masked_xent_all_ignored_rows():
@@ -322,6 +362,67 @@ def test_ffn_fused_gelu_pipe256_route():
     yr = torch.nn.functional.linear(g, w2.float(), b2.float())
     assert torch.allclose(y.float(), yr, rtol=0.05, atol=0.05), \
         (y.float() - yr).abs().max()
+
+
+def test_ffn_fused_gelu_pipe256_route_bwd():
+    """Backward at the 256²-route FFN shape: the fc2-dx GEMM with the gelu'
+    epilogue runs at M=4096, N=4096, K=256 — the TN pipe by default, the
+    transpose-plus-pipe256 route under MPIAMD_GELUBWD_WT=1, and the
+    recompute-tanh writers under MPIAMD_GELU_DERIV=0.
+
+    First the GEMM alone: linear_gelu_dgrad against fp32 (dy·w2) ⊙ gelu'(h),
+    max error over max |reference| with NO absolute floor. Budget: the bf16
+    store of dh is 2^-8 relative (bf16 unit roundoff); the saved operand is
+    bf16 too — gelu'(h) itself (another 2^-8 relative) or, under
+    GELU_DERIV=0, h with |δh| <= 2^-8·|h| and |gelu''| <= 1.13, i.e.
+    |δgelu'| <= 0.005 where |h| <= 1 and less beyond, where gelu'' decays;
+    the fp32 accumulation over K=256 is negligible. Together under
+    2·2^-8 + 0.001 = 0.009 of the scale; the bound is 0.02.
+    One output tile left unwritten, a dropped k-tile or a transposed w2
+    moves the error to the order of the scale itself.
+
+    Then all five FFN gradients against the fp32 torch FFN under a
+    sum-of-squares loss, so that they are O(1) and the bound is purely
+    relative (0.08 of the max, as in test_ffn_fused_gelu_matches_fp32)."""
+    from mpi_operator_amd.ops import functional as Fx
+    from mpi_operator_amd.ops import hip_ext
+    from mpi_operator_amd.ops import reference as ref_ops
+    ext = hip_ext()
+    torch.manual_seed(19)
+    M, H, I = 4096, 256, 4096
+    x = (torch.randn(M, H, device="cuda") * 0.5).to(torch.bfloat16)
+    w1 = (torch.randn(I, H, device="cuda") * 0.05).to(torch.bfloat16)
+    b1 = torch.randn(I, device="cuda").to(torch.bfloat16) * 0.1
+    w2 = (torch.randn(H, I, device="cuda") * 0.05).to(torch.bfloat16)
+    b2 = torch.randn(H, device="cuda").to(torch.bfloat16) * 0.1
+    dy = (torch.rand(M, H, device="cuda") * 2 - 1).to(torch.bfloat16)
+
+    _, aux = ext.linear_gelu_fwd(x, w1, b1)
+    dh = ext.linear_gelu_dgrad(dy, w2, aux)
+    h_ref = x.float() @ w1.float().t() + b1.float()
+    dh_ref = (dy.float() @ w2.float()) * ref_ops.dgelu(h_ref)
+    err = (dh.float() - dh_ref).abs().max().item()
+    scale = dh_ref.abs().max().item()
+    print("fc2-dx err", err, "scale", scale)
+    assert err < 0.02 * scale, (err, scale)
+
+    args = [t.clone().requires_grad_(True) for t in (x, w1, b1, w2, b2)]
+    y = Fx.ffn(*args)
+    y.float().square().sum().backward()
+
+    ref = [t.float().clone().requires_grad_(True) for t in (x, w1, b1, w2, b2)]
+    h = torch.nn.functional.linear(ref[0], ref[1], ref[2])
+    g = torch.nn.functional.gelu(h, approximate="tanh")
+    yr = torch.nn.functional.linear(g, ref[3], ref[4])
+    yr.square().sum().backward()
+
+    assert torch.allclose(y.float(), yr, rtol=0.05, atol=0.05), \
+        (y.float() - yr).abs().max()
+    for a, r, name in zip(args, ref, "x w1 b1 w2 b2".split()):
+        num = (a.grad.float() - r.grad).abs().max().item()
+        den = r.grad.abs().max().item()
+        print(name, "grad err", num, "scale", den)
+        assert num < 0.08 * den, (name, num, den)
 
 
 def test_fused_attention_backward_matches_torch():

@@ -39,6 +39,17 @@ def test_gemm_nt_matches_matmul(shape, c_f32):
     _gemm_case(*shape, c_f32)
 
 
+@pytest.mark.parametrize("c_f32", [False, True])
+def test_gemm_nt256_default_route(c_f32):
+    """Full 256² tiles with K % 64 == 32 take the BK=32 3-buffer kernel
+    (gemm256.h) with nothing set — every 256² shape above has K % 64 == 0
+    and so runs the 4-phase pipeline instead. (8192, 1024, 96) is the
+    smallest such grid at the 128-workgroup occupancy floor."""
+    from mpi_operator_amd.ops import hip_ext
+    assert hip_ext().nt_route(8192, 1024, 96) == "nt256"
+    _gemm_case(8192, 1024, 96, c_f32)
+
+
 def test_gemm_identity_asymmetric():
     """A=I with asymmetric B: catches row/col-swapped C writes."""
     from mpi_operator_amd.ops import hip_ext

@@ -188,12 +188,16 @@ def test_linear_fwd_bwd():
     assert relerr(db, dy.float().sum(0)) < 0.01
 
 
-def test_softmax_xent():
+@pytest.mark.parametrize("V", [10, 1000])
+def test_softmax_xent(V):
+    """V=10 is the SimpleCNN head: most of a block's 256 threads own no
+    column. Two rows pin their target to the first and the last column."""
     from mpi_operator_amd.ops import hip_ext
     ext = hip_ext()
     torch.manual_seed(41)
-    logits = ((torch.rand(64, 1000, device="cuda") * 2 - 1) * 4).to(torch.bfloat16)
-    tgt = torch.randint(0, 1000, (64,), device="cuda")
+    logits = ((torch.rand(64, V, device="cuda") * 2 - 1) * 4).to(torch.bfloat16)
+    tgt = torch.randint(0, V, (64,), device="cuda")
+    tgt[0], tgt[1] = 0, V - 1
     loss, probs = ext.softmax_xent_fwd(logits, tgt)
     lr_, pr = ref.softmax_cross_entropy_fwd(logits.float().cpu(), tgt.cpu())
     assert abs(loss.item() - lr_.item()) < 2e-3 * abs(lr_.item()) + 1e-3
