@@ -36,7 +36,8 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         if x.is_cuda and self.training and torch.is_grad_enabled():
             # fused block: residual add folded into bn3's apply pass, join
-            # gradient summed inside conv1's dgrad epilogue (ops/fused_block)
+            # gradient summed in one streaming kernel that also emits the
+            # previous block's BN-backward statistics (ops/fused_block)
             from ..ops.fused_block import fused_bottleneck
             return fused_bottleneck(x, self)
         identity = x if self.downsample is None else self.downsample(x)

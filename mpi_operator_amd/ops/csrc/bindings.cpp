@@ -187,6 +187,12 @@ hipError_t bn_bwd_pre_launch(const float *, int, const void *, const void *,
                              const float *, const float *, int, void *,
                              float *, float *, float *, float *, float *, long,
                              int, hipStream_t);
+int bn_stats_grid(long, int);
+hipError_t bn_join_stats_launch(const void *, const uint8_t *, const void *,
+                                void *, const uint8_t *, const void *,
+                                const float *, const float *, float *,
+                                const void *, const float *, const float *,
+                                float *, long, int, hipStream_t);
 hipError_t bn_fwd_train_pre_launch(const float *, int, const void *,
                                    const void *, const float *, const float *,
                                    float, int, void *, uint8_t *, float *,
@@ -563,6 +569,76 @@ static std::vector<Tensor> bn_bwd_pre(const Tensor &dy, const Tensor &slab,
                         k1.data_ptr<float>(), k2.data_ptr<float>(),
                         k3.data_ptr<float>(), M, C, cur_stream()));
   return {dx, dgamma, dbeta};
+}
+
+// Residual-join gradient fused with the backward partial stats of the BN
+// layer(s) that take it as their dy (the previous bottleneck's bn3 and, with
+// ds_x given, its downsample BN):
+//   jmask given: dxt = a·jmask + b (add_relu_bwd_add_mask), else dxt = a + b
+//   (add_bf16). cons_x/mean/invstd are the consumer BN's saved tensors,
+//   cons_mask the ReLU bitmask both consumers gate dxt by.
+// Returns (dxt, slab[, slab_ds]), each slab [rows][2][C] for bn_bwd_pre.
+static std::vector<Tensor> join_bwd_stats(
+    const Tensor &a, const Tensor &jmask, const Tensor &b,
+    const Tensor &cons_x, const Tensor &cons_mean, const Tensor &cons_invstd,
+    const Tensor &cons_mask, const Tensor &ds_x, const Tensor &ds_mean,
+    const Tensor &ds_invstd) {
+  check_cl_bf16(a, "a");
+  check_cl_bf16(b, "b");
+  check_cl_bf16(cons_x, "cons_x");
+  const HIPDeviceGuard guard(a.device());
+  int N = a.size(0), C = a.size(1), H = a.size(2), W = a.size(3);
+  long M = (long)N * H * W;
+  TORCH_CHECK(C % 8 == 0 && C / 8 <= 256, "join_bwd_stats needs C%8==0, C<=2048");
+  TORCH_CHECK(M >= 1, "empty tensor");
+  TORCH_CHECK(b.sizes() == a.sizes() && cons_x.sizes() == a.sizes(),
+              "b and cons_x must have a's shape");
+  auto check_stat = [&](const Tensor &t, const char *name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                    t.is_contiguous() && t.numel() == C,
+                name, " must be a contiguous fp32 [C] GPU tensor");
+  };
+  auto check_mask = [&](const Tensor &t, const char *name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kByte &&
+                    t.is_contiguous() && t.numel() == M * (C / 8),
+                name, " must be a contiguous uint8 [M][C/8] GPU tensor");
+  };
+  check_stat(cons_mean, "cons_mean");
+  check_stat(cons_invstd, "cons_invstd");
+  check_mask(cons_mask, "cons_mask");
+  const uint8_t *jp = nullptr;
+  if (jmask.defined() && jmask.numel() > 0) {
+    check_mask(jmask, "jmask");
+    jp = jmask.data_ptr<uint8_t>();
+  }
+  const bool has_ds = ds_x.defined() && ds_x.numel() > 0;
+  auto f32 = a.options().dtype(at::kFloat);
+  long rows = bn_stats_grid(M, C);
+  Tensor dxt = empty_cl_bf16(N, C, H, W, a);
+  Tensor slab = at::empty({rows, 2, (long)C}, f32);
+  Tensor slab_ds;
+  const void *xdp = nullptr;
+  const float *mdp = nullptr, *vdp = nullptr;
+  float *sdp = nullptr;
+  if (has_ds) {
+    check_cl_bf16(ds_x, "ds_x");
+    TORCH_CHECK(ds_x.sizes() == a.sizes(), "ds_x must have a's shape");
+    check_stat(ds_mean, "ds_mean");
+    check_stat(ds_invstd, "ds_invstd");
+    slab_ds = at::empty({rows, 2, (long)C}, f32);
+    xdp = ds_x.data_ptr();
+    mdp = ds_mean.data_ptr<float>();
+    vdp = ds_invstd.data_ptr<float>();
+    sdp = slab_ds.data_ptr<float>();
+  }
+  CHK(bn_join_stats_launch(a.data_ptr(), jp, b.data_ptr(), dxt.data_ptr(),
+                           cons_mask.data_ptr<uint8_t>(), cons_x.data_ptr(),
+                           cons_mean.data_ptr<float>(),
+                           cons_invstd.data_ptr<float>(),
+                           slab.data_ptr<float>(), xdp, mdp, vdp, sdp, M, C,
+                           cur_stream()));
+  if (has_ds) return {dxt, slab, slab_ds};
+  return {dxt, slab};
 }
 
 // ------------------------- pooling -------------------------
@@ -1233,6 +1309,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("fuse_epilogue") = true);
   m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
   m.def("bn_bwd_pre", &bn_bwd_pre);
+  m.def("join_bwd_stats", &join_bwd_stats);
   m.def("bn_fwd_train_pre", &bn_fwd_train_pre);
   m.def("conv2d_wgrad", &conv2d_wgrad);
   m.def("conv2d_dgrad_acc", &conv2d_dgrad_acc);
