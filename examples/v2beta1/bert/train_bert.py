@@ -14,8 +14,8 @@ import torch
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..", "..")))
 
 from mpi_operator_amd import parallel as hvd
-from mpi_operator_amd.models.bert import bert_large, bert_base, to_mi355x_bert
-from mpi_operator_amd.optim import FusedSGD
+from mpi_operator_amd.models.bert import bert_large, bert_base, bert_param_groups, to_mi355x_bert
+from mpi_operator_amd.optim import FusedAdamW, FusedLAMB, FusedSGD
 
 
 def synthetic_batch(batch, seq, vocab, device):
@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8, help="per-GPU sequences")
     ap.add_argument("--seq", type=int, default=128)
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lamb"])
     args = ap.parse_args()
 
     hvd.init()
@@ -45,7 +46,12 @@ def main():
     if use_cuda:
         model = to_mi355x_bert(model, device)
     model.train()
-    opt = FusedSGD(model.parameters(), lr=1e-4, momentum=0.9)
+    if args.optimizer == "sgd":
+        opt = FusedSGD(model.parameters(), lr=1e-4, momentum=0.9)
+    elif args.optimizer == "adamw":
+        opt = FusedAdamW(bert_param_groups(model, 0.01), lr=1e-4)
+    else:
+        opt = FusedLAMB(bert_param_groups(model, 0.01), lr=2e-3)
     opt = hvd.DistributedOptimizer(opt, model.named_parameters())
     hvd.broadcast_parameters(model, 0)
 

@@ -287,6 +287,23 @@ class BertForPreTraining(nn.Module):
         return l_mlm + l_nsp
 
 
+def bert_param_groups(model: nn.Module, weight_decay: float = 0.01):
+    """Optimizer param groups with the usual BERT exemption: no weight decay
+    on biases and LayerNorm parameters."""
+    no_decay = {id(p) for mod in model.modules() if isinstance(mod, LayerNorm)
+                for p in mod.parameters(recurse=False)}
+    decay, exempt = [], []
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        if id(p) in no_decay or name.endswith("bias"):
+            exempt.append(p)
+        else:
+            decay.append(p)
+    return [{"params": decay, "weight_decay": weight_decay},
+            {"params": exempt, "weight_decay": 0.0}]
+
+
 def to_mi355x_bert(model: BertForPreTraining, device) -> BertForPreTraining:
     """bf16 working weights on the GPU, with LayerNorm params and linear
     biases kept fp32: the HIP kernels consume them as fp32 operands anyway

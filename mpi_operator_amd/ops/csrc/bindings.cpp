@@ -104,6 +104,24 @@ struct SgdDesc {
 };
 hipError_t sgd_step_launch(const SgdDesc *, int, int, float, float, float, int,
                            hipStream_t);
+struct OptDesc {
+  const void *grad;
+  float *master;
+  float *m;
+  float *v;
+  uint16_t *out;
+  long numel;
+};
+int optim_block_count(const OptDesc *, int);
+hipError_t optim_tick_launch(float *, const float *, int, double, double,
+                             double, hipStream_t);
+hipError_t l2norm_partials_launch(const OptDesc *, int, int, float *, int,
+                                  hipStream_t);
+hipError_t adam_step_launch(const OptDesc *, int, int, const float *, double,
+                            double, double, double, int, hipStream_t);
+hipError_t lamb_step_launch(const OptDesc *, int, int, const float *, float *,
+                            float *, int, float *, int, double, double, double,
+                            double, int, hipStream_t);
 int bn_grid_cap(int);
 hipError_t bn_fwd_train_launch(const void *, const void *, const float *,
                                const float *, float, int, void *, uint8_t *,
@@ -1235,6 +1253,142 @@ static void sgd_step(std::vector<Tensor> masters, std::vector<Tensor> grads,
                           cur_stream()));
 }
 
+// ------------------------- adamw / lamb -------------------------
+// Descriptors grouped by grad dtype (0: f32, 1: bf16), as sgd_step does.
+// Every stream of a tensor must be dense with the param's numel: the kernels
+// index all of them with one linear offset.
+struct OptGroups {
+  std::vector<OptDesc> by_dtype[2];
+  int blocks = 0;  // partials-slab slots the whole list needs
+  int tensors = 0;
+};
+
+static OptGroups opt_groups(const std::vector<Tensor> &masters,
+                            const std::vector<Tensor> &grads,
+                            const std::vector<Tensor> &exp_avgs,
+                            const std::vector<Tensor> &exp_avg_sqs,
+                            const std::vector<Tensor> &outs,
+                            const Tensor &scalars) {
+  size_t n = masters.size();
+  TORCH_CHECK(n > 0 && grads.size() == n && exp_avgs.size() == n &&
+              exp_avg_sqs.size() == n && outs.size() == n,
+              "optimizer step: tensor lists must be non-empty and equal length");
+  TORCH_CHECK(scalars.is_cuda() && scalars.scalar_type() == at::kFloat &&
+              scalars.is_contiguous() && scalars.numel() >= 8,
+              "optimizer step: scalar block must be >= 8 fp32 on GPU");
+  OptGroups g;
+  for (size_t i = 0; i < n; ++i) {
+    const Tensor &w = masters[i], &gr = grads[i], &m = exp_avgs[i],
+                 &v = exp_avg_sqs[i], &o = outs[i];
+    const int64_t ne = w.numel();
+    const bool gbf = gr.scalar_type() == at::kBFloat16;
+    TORCH_CHECK(w.is_cuda() && gr.is_cuda() && m.is_cuda() && v.is_cuda(),
+                "optimizer step: tensors must be on GPU");
+    TORCH_CHECK(w.scalar_type() == at::kFloat && m.scalar_type() == at::kFloat &&
+                v.scalar_type() == at::kFloat &&
+                (gbf || gr.scalar_type() == at::kFloat),
+                "optimizer step: master/exp_avg/exp_avg_sq fp32, grad fp32 or bf16");
+    TORCH_CHECK(gr.numel() == ne && m.numel() == ne && v.numel() == ne &&
+                w.is_non_overlapping_and_dense() &&
+                gr.is_non_overlapping_and_dense() &&
+                m.is_non_overlapping_and_dense() &&
+                v.is_non_overlapping_and_dense(),
+                "optimizer step: tensor ", i, " streams must be dense and equal-sized");
+    OptDesc d;
+    d.grad = gr.data_ptr();
+    d.master = w.data_ptr<float>();
+    d.m = m.data_ptr<float>();
+    d.v = v.data_ptr<float>();
+    d.out = nullptr;
+    if (o.numel() > 0) {
+      TORCH_CHECK(o.is_cuda() && o.scalar_type() == at::kBFloat16 &&
+                  o.numel() == ne && o.is_non_overlapping_and_dense(),
+                  "optimizer step: working copy ", i, " must be dense bf16");
+      d.out = (uint16_t *)o.data_ptr();
+    }
+    d.numel = ne;
+    g.by_dtype[gbf ? 1 : 0].push_back(d);
+  }
+  for (int t = 0; t < 2; ++t) {
+    g.blocks += optim_block_count(g.by_dtype[t].data(), (int)g.by_dtype[t].size());
+    g.tensors += (int)g.by_dtype[t].size();
+  }
+  return g;
+}
+
+static void check_slab(const Tensor &t, int64_t need, const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+              t.is_contiguous() && t.numel() >= need,
+              "optimizer step: ", name, " must hold >= ", need, " fp32 on GPU");
+}
+
+// grad-norm partials (only when clipping) and the step-state tick
+static void opt_tick(const OptGroups &g, const Tensor &scalars,
+                     const Tensor &partials, double beta1, double beta2,
+                     double max_grad_norm) {
+  const bool clip = max_grad_norm > 0.0;
+  if (clip) {
+    check_slab(partials, g.blocks, "partials");
+    int base = 0;
+    for (int t = 0; t < 2; ++t) {
+      const auto &v = g.by_dtype[t];
+      if (v.empty()) continue;
+      CHK(l2norm_partials_launch(v.data(), (int)v.size(), t,
+                                 partials.data_ptr<float>(), base, cur_stream()));
+      base += optim_block_count(v.data(), (int)v.size());
+    }
+  }
+  CHK(optim_tick_launch(scalars.data_ptr<float>(),
+                        clip ? partials.data_ptr<float>() : nullptr, g.blocks,
+                        beta1, beta2, clip ? max_grad_norm : 0.0, cur_stream()));
+}
+
+static void adam_step(std::vector<Tensor> masters, std::vector<Tensor> grads,
+                      std::vector<Tensor> exp_avgs,
+                      std::vector<Tensor> exp_avg_sqs, std::vector<Tensor> outs,
+                      Tensor scalars, Tensor partials, double beta1,
+                      double beta2, double eps, double wd, bool adam_w_mode,
+                      double max_grad_norm) {
+  TORCH_CHECK(!masters.empty());
+  const HIPDeviceGuard guard(masters[0].device());
+  OptGroups g = opt_groups(masters, grads, exp_avgs, exp_avg_sqs, outs, scalars);
+  opt_tick(g, scalars, partials, beta1, beta2, max_grad_norm);
+  for (int t = 0; t < 2; ++t)
+    if (!g.by_dtype[t].empty())
+      CHK(adam_step_launch(g.by_dtype[t].data(), (int)g.by_dtype[t].size(), t,
+                           scalars.data_ptr<float>(), beta1, beta2, eps, wd,
+                           adam_w_mode ? 1 : 0, cur_stream()));
+}
+
+// partials: 3 slabs of `blocks` slots (grad norm | sum w^2 | sum u^2);
+// ratio: one slot per tensor
+static void lamb_step(std::vector<Tensor> masters, std::vector<Tensor> grads,
+                      std::vector<Tensor> exp_avgs,
+                      std::vector<Tensor> exp_avg_sqs, std::vector<Tensor> outs,
+                      Tensor scalars, Tensor partials, Tensor ratio,
+                      double beta1, double beta2, double eps, double wd,
+                      bool adam_w_mode, double max_grad_norm) {
+  TORCH_CHECK(!masters.empty());
+  const HIPDeviceGuard guard(masters[0].device());
+  OptGroups g = opt_groups(masters, grads, exp_avgs, exp_avg_sqs, outs, scalars);
+  check_slab(partials, 3 * (int64_t)g.blocks, "partials");
+  check_slab(ratio, g.tensors, "ratio");
+  opt_tick(g, scalars, partials, beta1, beta2, max_grad_norm);
+  float *pw = partials.data_ptr<float>() + g.blocks;
+  float *pu = pw + g.blocks;
+  int block_base = 0, tensor_base = 0;
+  for (int t = 0; t < 2; ++t) {
+    const auto &v = g.by_dtype[t];
+    if (v.empty()) continue;
+    CHK(lamb_step_launch(v.data(), (int)v.size(), t, scalars.data_ptr<float>(),
+                         pw, pu, block_base, ratio.data_ptr<float>(),
+                         tensor_base, beta1, beta2, eps, wd,
+                         adam_w_mode ? 1 : 0, cur_stream()));
+    block_base += optim_block_count(v.data(), (int)v.size());
+    tensor_base += (int)v.size();
+  }
+}
+
 // ------------------------- raw gemm (tests) -------------------------
 static Tensor gemm_nt_b(const Tensor &a, const Tensor &b, bool c_f32) {
   const HIPDeviceGuard guard(a.device());
@@ -1346,6 +1500,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_relu_bwd_add", &add_relu_bwd_add_b);
   m.def("add_relu_bwd_add_mask", &add_relu_bwd_add_mask_b);
   m.def("sgd_step", &sgd_step);
+  m.def("adam_step", &adam_step);
+  m.def("lamb_step", &lamb_step);
   m.def("gemm_nt", &gemm_nt_b);
   m.def("mfma_probe", [](const Tensor &a, const Tensor &b) {
     const HIPDeviceGuard guard(a.device());

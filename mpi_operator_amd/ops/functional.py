@@ -265,6 +265,47 @@ def sgd_momentum_step(params32, grads, momenta, bf16_outs, lr, momentum, weight_
         ref.sgd_momentum_step(params32, grads, momenta, bf16_outs, lr, momentum, weight_decay, nesterov)
 
 
+OPTIM_EPB = 8192  # elements per block of the multi-tensor optimizer kernels
+
+
+def optim_block_count(tensors) -> int:
+    """Slots one partials slab needs for `tensors` (one per kernel block)."""
+    return sum((t.numel() + OPTIM_EPB - 1) // OPTIM_EPB for t in tensors)
+
+
+def _hip_outs(bf16_outs):
+    return [o if o is not None else torch.empty(0) for o in bf16_outs]
+
+
+def adamw_step(params32, grads, exp_avgs, exp_avg_sqs, bf16_outs, scalars, partials,
+               beta1, beta2, eps, weight_decay, adam_w_mode=True, max_grad_norm=None):
+    """Fused multi-tensor AdamW (adam_w_mode) / Adam+L2: advances the device
+    step state in `scalars` (layout: reference.OPT_*), then updates fp32
+    masters and moments and refreshes the bf16 working copies. `partials`
+    (>= optim_block_count slots) is only touched when max_grad_norm is set."""
+    if params32 and params32[0].is_cuda:
+        hip_ext().adam_step(list(params32), list(grads), list(exp_avgs), list(exp_avg_sqs),
+                            _hip_outs(bf16_outs), scalars, partials, beta1, beta2, eps,
+                            weight_decay, bool(adam_w_mode), max_grad_norm or 0.0)
+    else:
+        ref.adamw_step(params32, grads, exp_avgs, exp_avg_sqs, bf16_outs, scalars,
+                       beta1, beta2, eps, weight_decay, adam_w_mode, max_grad_norm)
+
+
+def lamb_step(params32, grads, exp_avgs, exp_avg_sqs, bf16_outs, scalars, partials, ratio,
+              beta1, beta2, eps, weight_decay, adam_w_mode=True, max_grad_norm=None):
+    """Fused multi-tensor LAMB: stage 1 (moments + norm partials), per-tensor
+    trust ratio, stage 2 (apply). `partials` holds 3 slabs of
+    optim_block_count slots, `ratio` one slot per tensor."""
+    if params32 and params32[0].is_cuda:
+        hip_ext().lamb_step(list(params32), list(grads), list(exp_avgs), list(exp_avg_sqs),
+                            _hip_outs(bf16_outs), scalars, partials, ratio, beta1, beta2,
+                            eps, weight_decay, bool(adam_w_mode), max_grad_norm or 0.0)
+    else:
+        ref.lamb_step(params32, grads, exp_avgs, exp_avg_sqs, bf16_outs, scalars,
+                      beta1, beta2, eps, weight_decay, adam_w_mode, max_grad_norm)
+
+
 class AddReLUFn(torch.autograd.Function):
     """Fused residual add + ReLU (the Bottleneck join — hot elementwise)."""
 

@@ -121,6 +121,78 @@ def sgd_momentum_step(params32, grads32, momenta, bf16_outs, lr, momentum, weigh
             out.copy_(p.to(out.dtype))
 
 
+# Layout of the optimizers' per-group scalar block (8 fp32; slot 0 holds the
+# int32 step count as a bit pattern) — mirrors csrc/optimizer.hip.
+OPT_STEP, OPT_LR, OPT_BC1, OPT_BC2, OPT_CLIP = 0, 1, 2, 3, 4
+OPT_SCALARS = 8
+
+
+def optim_tick(scalars, grads, beta1, beta2, max_grad_norm=None):
+    """Advance the scalar block by one step (the reference of optim_tick_k):
+    step += 1, bias corrections in double, clip scale with
+    torch.nn.utils.clip_grad_norm_ semantics. Returns (lr, bc1, bc2, clip)
+    as Python floats — bc1/bc2 unrounded, as torch.optim computes them."""
+    step_i = scalars.view(torch.int32)[OPT_STEP:OPT_STEP + 1]
+    step_i += 1
+    step = int(step_i)
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    clip = 1.0
+    if max_grad_norm:
+        sq = sum(float(g.double().pow(2).sum()) for g in grads)
+        clip = min(1.0, max_grad_norm / (sq ** 0.5 + 1e-6))
+    scalars[OPT_BC1] = bc1
+    scalars[OPT_BC2] = bc2
+    scalars[OPT_CLIP] = clip
+    return float(scalars[OPT_LR]), bc1, bc2, clip
+
+
+def adamw_step(params32, grads, exp_avgs, exp_avg_sqs, bf16_outs, scalars,
+               beta1, beta2, eps, weight_decay, adam_w_mode=True,
+               max_grad_norm=None):
+    """torch.optim.AdamW (adam_w_mode) / torch.optim.Adam-with-L2 update on
+    fp32 masters, in torch's operation order; refreshes bf16 working copies."""
+    lr, bc1, bc2, clip = optim_tick(scalars, grads, beta1, beta2, max_grad_norm)
+    for p, g, m, v, out in zip(params32, grads, exp_avgs, exp_avg_sqs, bf16_outs):
+        gf = g.float()
+        if clip != 1.0:
+            gf = gf * clip
+        if adam_w_mode:
+            p.mul_(1.0 - lr * weight_decay)
+        elif weight_decay:
+            gf = gf.add(p, alpha=weight_decay)
+        m.lerp_(gf, 1.0 - beta1)
+        v.mul_(beta2).addcmul_(gf, gf, value=1.0 - beta2)
+        denom = (v.sqrt() / bc2 ** 0.5).add_(eps)
+        p.addcdiv_(m, denom, value=-lr / bc1)
+        if out is not None:
+            out.copy_(p.to(out.dtype))
+
+
+def lamb_step(params32, grads, exp_avgs, exp_avg_sqs, bf16_outs, scalars,
+              beta1, beta2, eps, weight_decay, adam_w_mode=True,
+              max_grad_norm=None):
+    """LAMB: Adam moments, u = m_hat / (sqrt(v_hat) + eps) + wd*w, per-tensor
+    trust ratio ||w|| / ||u|| (1 if either norm is 0), w -= lr * ratio * u."""
+    lr, bc1, bc2, clip = optim_tick(scalars, grads, beta1, beta2, max_grad_norm)
+    for p, g, m, v, out in zip(params32, grads, exp_avgs, exp_avg_sqs, bf16_outs):
+        gf = g.float()
+        if clip != 1.0:
+            gf = gf * clip
+        if not adam_w_mode and weight_decay:
+            gf = gf.add(p, alpha=weight_decay)
+        m.mul_(beta1).add_(gf, alpha=1.0 - beta1)
+        v.mul_(beta2).addcmul_(gf, gf, value=1.0 - beta2)
+        u = (m / bc1) / ((v / bc2).sqrt() + eps)
+        if adam_w_mode and weight_decay:
+            u = u.add(p, alpha=weight_decay)
+        nw, nu = float(p.norm()), float(u.norm())
+        ratio = nw / nu if (nw > 0 and nu > 0) else 1.0
+        p.add_(u, alpha=-lr * ratio)
+        if out is not None:
+            out.copy_(p.to(out.dtype))
+
+
 def masked_softmax_cross_entropy_fwd(logits, target, ignore_index=-100):
     """fp32 golden oracle for the MLM masked CE (mean over valid rows)."""
     x = logits.float()

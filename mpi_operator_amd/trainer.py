@@ -9,7 +9,7 @@ import time
 import torch
 
 from . import parallel as hvd
-from .optim import FusedSGD
+from .optim import FusedAdamW, FusedLAMB, FusedSGD
 from .parallel import DistributedOptimizer
 
 
@@ -37,11 +37,18 @@ class SyntheticImageData:
 
 
 def make_trainer(model, lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4,
-                 bucket_bytes: int | None = None):
+                 bucket_bytes: int | None = None, optimizer: str = "sgd"):
     """LR scaled by world size, as the Horovod example does
-    (reference tensorflow_mnist.py:123-130)."""
-    opt = FusedSGD(model.parameters(), lr=lr * hvd.size(), momentum=momentum,
-                   weight_decay=weight_decay)
+    (reference tensorflow_mnist.py:123-130). optimizer: "sgd" (momentum SGD,
+    the default), "adamw" or "lamb" (momentum is then unused)."""
+    if optimizer == "sgd":
+        opt = FusedSGD(model.parameters(), lr=lr * hvd.size(), momentum=momentum,
+                       weight_decay=weight_decay)
+    elif optimizer in ("adamw", "lamb"):
+        cls = FusedAdamW if optimizer == "adamw" else FusedLAMB
+        opt = cls(model.parameters(), lr=lr * hvd.size(), weight_decay=weight_decay)
+    else:
+        raise ValueError(f"unknown optimizer {optimizer!r}")
     kw = {}
     if bucket_bytes is not None:
         kw["bucket_bytes"] = bucket_bytes

@@ -3,6 +3,7 @@
 BASELINE.json measured standalone. Usage:
     python tools/bert_bench.py [--model bert_large] [--batch 32] [--seq 128]
                                [--steps 30] [--warmup 5]
+                               [--optimizer sgd|adamw|lamb]
 """
 import argparse
 import os
@@ -23,15 +24,21 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--graph", type=int, default=1)
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lamb"])
     args = ap.parse_args()
 
     from mpi_operator_amd.models import bert as B
-    from mpi_operator_amd.optim import FusedSGD
+    from mpi_operator_amd.optim import FusedAdamW, FusedLAMB, FusedSGD
 
     torch.manual_seed(0)
     m = B.to_mi355x_bert(getattr(B, args.model)(), "cuda")
     m.train()
-    opt = FusedSGD(m.parameters(), lr=1e-3, momentum=0.9)
+    if args.optimizer == "sgd":
+        opt = FusedSGD(m.parameters(), lr=1e-3, momentum=0.9)
+    elif args.optimizer == "adamw":
+        opt = FusedAdamW(B.bert_param_groups(m, 0.01), lr=1e-4)
+    else:
+        opt = FusedLAMB(B.bert_param_groups(m, 0.01), lr=2e-3)
     ids = torch.randint(0, m.cfg.vocab_size, (args.batch, args.seq), device="cuda")
     mlm_labels = ids.clone()
     nsp = torch.randint(0, 2, (args.batch,), device="cuda")
