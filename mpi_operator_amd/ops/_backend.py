@@ -29,6 +29,10 @@ def _try_load():
         import torch  # noqa: F401  (the .so links against libtorch)
 
         _ext = importlib.import_module("mpi_operator_amd.ops._mpi_amd_hip")
+        # MPIAMD_EPI_VEC (default "1"): 16-byte-store GEMM epilogues;
+        # "0" keeps the one-element-per-lane stores (A/B lever)
+        if os.environ.get("MPIAMD_EPI_VEC", "1") == "0":
+            _ext.set_epilogue_vec(False)
     except Exception as e:  # pragma: no cover - exercised on GPU boxes only
         _ext_err = e
 

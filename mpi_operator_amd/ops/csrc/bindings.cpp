@@ -80,6 +80,7 @@ extern "C" {
 // route introspection: each TU reports the knobs its own launchers resolve
 void gemm_route_knobs(int *);  // gemm.hip, 15 values
 int gemm_nt_route_id(int, int, int, int);
+int gemm_set_epilogue_vec(int); // gemm.hip: returns the previous value
 void conv_route_knobs(int *);  // conv.hip, 3 values
 void ln_route_knobs(int *);    // layernorm.hip, 2 values
 void bn_route_knobs(int *);    // batchnorm.hip, 2 values
@@ -1451,6 +1452,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("route_info", &route_info);
   m.def("nt_route", &nt_route, py::arg("M"), py::arg("N"), py::arg("K"),
         py::arg("splits") = 1);
+  // 16-byte-store GEMM epilogue on/off for the whole process; returns the
+  // previous value (A/B lever and the tests' scalar reference)
+  m.def("set_epilogue_vec",
+        [](bool on) { return gemm_set_epilogue_vec(on ? 1 : 0) != 0; });
   // does the fc2-dx GEMM of dy [M][K] · w2 [K][N] take the transpose-plus-
   // pipe256 route (MPIAMD_GELUBWD_WT)? The route's own predicate.
   m.def("gelubwd_wt_route", [](int M, int N, int K) {

@@ -438,6 +438,14 @@ extern "C" void gemm_route_knobs(int *out) {
   out[14] = gelubwd_wt_on();
 }
 
+// Process-wide switch of the 16-byte-store epilogue (mix_gemm.h): returns
+// the previous value. The one flag every launcher of the library reads —
+// conv.hip included (inline variable). Not an environment knob: the Python
+// side owns MPIAMD_EPI_VEC and calls this once at load.
+extern "C" int gemm_set_epilogue_vec(int on) {
+  return g_epilogue_vec.exchange(on != 0) ? 1 : 0;
+}
+
 // nt_gemm_route for a dense NT problem (kdim == K on both operands,
 // ldc == N): 0 pipe256, 1 nt256, 2 pipemix, 3 glds, 4 reg.
 extern "C" int gemm_nt_route_id(int M, int N, int K, int splits) {

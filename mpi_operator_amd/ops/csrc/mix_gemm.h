@@ -22,6 +22,9 @@
 // global data during tile t's MFMAs, write it to LDS after them) — the
 // measured-best register-staging form for this 2-barrier structure.
 #pragma once
+#include <atomic>
+#include <cstdint>
+
 #include "mfma_tile.h"
 
 constexpr int MXP = 9; // slots per LDS image row (pitch 144 B)
@@ -135,17 +138,33 @@ typedef __attribute__((ext_vector_type(16))) float float16v;
 // sub-image back into an NHWC tensor (stride-2 dgrad decomposition).
 // Writer concept: RowCtx row_ctx(row) hoists the per-row address work out
 // of the column loop; store_*(ptr, ctx, col, v) places one value.
+//
+// Vector path (optional, flagged by VEC): store_bf16x8 / store_f32x4 place 8
+// already-rounded bf16 or 4 fp32 values of ONE row at a column that is a
+// multiple of 8 / 4 with a single 16-byte store. The row-major epilogues of
+// pipe_mix8_k and pipe256x16_gemm_k use it when the launcher finds the
+// launch eligible (vec_ok() + epilogue_vec_eligible() below); writers without
+// it (VEC = false) keep the one-element-per-lane epilogue.
 struct LinearWriter {
   static constexpr bool ACC = false;
   static constexpr bool STATS = false;
+  static constexpr bool VEC = true;
   long ldc;
   typedef long RowCtx;
+  // host: every row base lands on a 16-byte boundary for group width g
+  bool vec_ok(int g) const { return ldc % g == 0; }
   DEV_INLINE RowCtx row_ctx(int row) const { return (long)row * ldc; }
   DEV_INLINE void store_f32(float *p, RowCtx b, int col, float v) const {
     p[b + col] = v;
   }
   DEV_INLINE void store_bf16(uint16_t *p, RowCtx b, int col, float v) const {
     p[b + col] = f2bf(v);
+  }
+  DEV_INLINE void store_f32x4(float *p, RowCtx b, int col, float4v v) const {
+    *(float4v *)(p + b + col) = v;
+  }
+  DEV_INLINE void store_bf16x8(uint16_t *p, RowCtx b, int col, ushort8 v) const {
+    *(ushort8 *)(p + b + col) = v;
   }
 };
 
@@ -155,6 +174,7 @@ struct LinearWriter {
 struct BiasWriter {
   static constexpr bool ACC = false;
   static constexpr bool STATS = false;
+  static constexpr bool VEC = false;
   long ldc;
   const float *bias;
   typedef long RowCtx;
@@ -206,6 +226,7 @@ DEV_INLINE float gelu_pair_f(float x, float &dg) {
 struct GeluBiasWriter {
   static constexpr bool ACC = false;
   static constexpr bool STATS = false;
+  static constexpr bool VEC = false;
   long ldc;
   const float *bias;
   uint16_t *deriv; // gelu'(h), bf16, same layout as C (saved for backward)
@@ -229,6 +250,7 @@ struct GeluBiasWriter {
 struct GeluBwdWriter {
   static constexpr bool ACC = false;
   static constexpr bool STATS = false;
+  static constexpr bool VEC = false;
   long ldc;
   const uint16_t *deriv; // gelu'(h) saved by GeluBiasWriter — exp-free
   typedef long RowCtx;
@@ -246,6 +268,7 @@ struct GeluBwdWriter {
 struct GeluBiasPreWriter {
   static constexpr bool ACC = false;
   static constexpr bool STATS = false;
+  static constexpr bool VEC = false;
   long ldc;
   const float *bias;
   uint16_t *pre; // h (pre-activation), bf16
@@ -266,6 +289,7 @@ struct GeluBiasPreWriter {
 struct GeluBwdPreWriter {
   static constexpr bool ACC = false;
   static constexpr bool STATS = false;
+  static constexpr bool VEC = false;
   long ldc;
   const uint16_t *pre;
   typedef long RowCtx;
@@ -303,6 +327,7 @@ struct GeluBwdPreWriter {
 struct BnStatsWriter {
   static constexpr bool ACC = false;
   static constexpr bool STATS = true;
+  static constexpr bool VEC = false;
   long ldc;
   float *slab; // [ceil(M/64)][2][C]
   int C;
@@ -363,8 +388,26 @@ struct BnStatsWriter {
 struct LinearAccWriter {
   static constexpr bool ACC = true;
   static constexpr bool STATS = false;
+  static constexpr bool VEC = true; // acc_bf16x8 takes fp32, not rounded bf16
   long ldc;
   typedef long RowCtx;
+  bool vec_ok(int g) const { return ldc % g == 0; }
+  DEV_INLINE void store_f32x4(float *p, RowCtx b, int col, float4v v) const {
+    float4v o = *(const float4v *)(p + b + col);
+    *(float4v *)(p + b + col) = o + v;
+  }
+  // 16-byte read-modify-write: the sum is formed in fp32 from the UNROUNDED
+  // accumulator and rounded once, exactly as store_bf16 does per element
+  DEV_INLINE void acc_bf16x8(uint16_t *p, RowCtx b, int col, float4v lo,
+                             float4v hi) const {
+    ushort8 o = *(const ushort8 *)(p + b + col), r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      r[j] = f2bf(lo[j] + bf2f(o[j]));
+      r[4 + j] = f2bf(hi[j] + bf2f(o[4 + j]));
+    }
+    *(ushort8 *)(p + b + col) = r;
+  }
   DEV_INLINE RowCtx row_ctx(int row) const { return (long)row * ldc; }
   DEV_INLINE void store_f32(float *p, RowCtx b, int col, float v) const {
     p[b + col] += v;
@@ -377,8 +420,10 @@ struct LinearAccWriter {
 struct Stride2Writer {
   static constexpr bool ACC = false;
   static constexpr bool STATS = false;
+  static constexpr bool VEC = true;
   int W2, H2, ph, pw, W, H, C;
   typedef long RowCtx;
+  bool vec_ok(int g) const { return C % g == 0; } // pixel bases are k*C
   DEV_INLINE RowCtx row_ctx(int row) const {
     int w_ = row % W2;
     long t = row / W2;
@@ -392,6 +437,12 @@ struct Stride2Writer {
   DEV_INLINE void store_bf16(uint16_t *p, RowCtx b, int col, float v) const {
     p[b + col] = f2bf(v);
   }
+  DEV_INLINE void store_f32x4(float *p, RowCtx b, int col, float4v v) const {
+    *(float4v *)(p + b + col) = v;
+  }
+  DEV_INLINE void store_bf16x8(uint16_t *p, RowCtx b, int col, ushort8 v) const {
+    *(ushort8 *)(p + b + col) = v;
+  }
 };
 
 // 1x1 stride-2 dgrad: parity (pad%2, pad%2) is the ONLY contributor, so the
@@ -399,7 +450,9 @@ struct Stride2Writer {
 struct Stride2ZeroWriter {
   static constexpr bool ACC = false;
   static constexpr bool STATS = false;
+  static constexpr bool VEC = true;
   int W2, H2, ph, pw, W, H, C;
+  bool vec_ok(int g) const { return C % g == 0; }
   struct RowCtx {
     long base;
     int sib; // bit0: w+1 valid, bit1: h+1 valid
@@ -426,7 +479,129 @@ struct Stride2ZeroWriter {
       if (c.sib & 1) p[c.base + (long)W * C + C + col] = 0;
     }
   }
+  DEV_INLINE void store_f32x4(float *p, RowCtx c, int col, float4v v) const {
+    *(float4v *)(p + c.base + col) = v;
+  }
+  DEV_INLINE void store_bf16x8(uint16_t *p, RowCtx c, int col, ushort8 v) const {
+    const ushort8 z{0, 0, 0, 0, 0, 0, 0, 0};
+    *(ushort8 *)(p + c.base + col) = v;
+    if (c.sib & 1) *(ushort8 *)(p + c.base + C + col) = z;
+    if (c.sib & 2) {
+      *(ushort8 *)(p + c.base + (long)W * C + col) = z;
+      if (c.sib & 1) *(ushort8 *)(p + c.base + (long)W * C + C + col) = z;
+    }
+  }
 };
+
+// ---- row-major (16-byte store) epilogue --------------------------------
+// Process-wide switch, set through the extension's set_epilogue_vec(); the
+// launchers read it per launch. One object for every translation unit of
+// the library (C++17 inline variable).
+inline std::atomic<bool> g_epilogue_vec{true};
+
+// Per-launch eligibility of the 16-byte store path: whole column groups
+// (N % g), 16-byte aligned output pointer, row bases (the writer's vec_ok)
+// and split-K slab stride. g = 4 for fp32, 8 for bf16.
+template <class WR>
+static inline bool epilogue_vec_eligible(const WR &wrt, const void *c, int N,
+                                         bool c_f32, int splits,
+                                         long split_stride) {
+  if constexpr (!WR::VEC) {
+    return false;
+  } else {
+    const int g = c_f32 ? 4 : 8;
+    return g_epilogue_vec.load(std::memory_order_relaxed) && N % g == 0 &&
+           ((uintptr_t)c & 15) == 0 && wrt.vec_ok(g) &&
+           (splits <= 1 || split_stride % g == 0);
+  }
+}
+
+typedef float __attribute__((may_alias)) f32_alias;
+typedef uint16_t __attribute__((may_alias)) u16_alias;
+typedef float4v __attribute__((may_alias)) float4v_alias;
+typedef ushort8 __attribute__((may_alias)) ushort8_alias;
+
+// One 32-row band of a wave's accumulators, NF 32x32 fragments side by
+// side (32·NF columns), through a WAVE-PRIVATE LDS region of 4·NF KiB:
+// the MFMA C/D map (lane = column, 16 regs = rows) is written row-major
+// (unpadded pitch: the b32/b16 writes of 32 consecutive columns and the
+// b128 reads below are bank-conflict-free for the ds_read_b128 lane
+// groups), read back as 16-byte row segments and stored through the
+// writer's vector path. bf16 rounds per element BEFORE staging (same f2bf
+// as the scalar path). Only wave-local ordering is needed — LDS operations
+// of one wave execute in order — so no s_barrier in here; the caller
+// barriers ONCE before the first band, when other waves may still be
+// reading the operand images this region overlays.
+template <int NF, bool C_F32, class WR>
+DEV_INLINE void vec_epilogue_band(const WR &wrt, void *cptr, void *wave_lds,
+                                  const float16v *a, int lane, int row_base,
+                                  int col_base, int M, int N) {
+  constexpr int PITCH = NF * 32; // elements per staged row
+  const int lc = lane & 31, lr = 4 * (lane >> 5);
+  if constexpr (WR::ACC && !C_F32) {
+    // accumulating writer: stage fp32 (the old value joins before rounding)
+    f32_alias *w = (f32_alias *)wave_lds;
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        w[((r & 3) + 8 * (r >> 2) + lr) * PITCH + f * 32 + lc] = a[f][r];
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    constexpr int LPR = NF * 4, RPP = 64 / LPR;
+    const int rl0 = lane / LPR, cg = (lane % LPR) * 8;
+#pragma unroll
+    for (int p = 0; p < 32 / RPP; ++p) {
+      int rl = p * RPP + rl0;
+      float4v lo = *(const float4v_alias *)(w + rl * PITCH + cg);
+      float4v hi = *(const float4v_alias *)(w + rl * PITCH + cg + 4);
+      int row = row_base + rl, col = col_base + cg;
+      if (row < M && col < N)
+        wrt.acc_bf16x8((uint16_t *)cptr, wrt.row_ctx(row), col, lo, hi);
+    }
+  } else if constexpr (C_F32) {
+    f32_alias *w = (f32_alias *)wave_lds;
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        w[((r & 3) + 8 * (r >> 2) + lr) * PITCH + f * 32 + lc] = a[f][r];
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    constexpr int LPR = NF * 8, RPP = 64 / LPR; // lanes per row, rows per pass
+    const int rl0 = lane / LPR, cg = (lane % LPR) * 4;
+#pragma unroll
+    for (int p = 0; p < 32 / RPP; ++p) {
+      int rl = p * RPP + rl0;
+      float4v v = *(const float4v_alias *)(w + rl * PITCH + cg);
+      int row = row_base + rl, col = col_base + cg;
+      if (row < M && col < N)
+        wrt.store_f32x4((float *)cptr, wrt.row_ctx(row), col, v);
+    }
+  } else {
+    u16_alias *w = (u16_alias *)wave_lds;
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        w[((r & 3) + 8 * (r >> 2) + lr) * PITCH + f * 32 + lc] = f2bf(a[f][r]);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    constexpr int LPR = NF * 4, RPP = 64 / LPR;
+    const int rl0 = lane / LPR, cg = (lane % LPR) * 8;
+#pragma unroll
+    for (int p = 0; p < 32 / RPP; ++p) {
+      int rl = p * RPP + rl0;
+      ushort8 v = *(const ushort8_alias *)(w + rl * PITCH + cg);
+      int row = row_base + rl, col = col_base + cg;
+      if (row < M && col < N)
+        wrt.store_bf16x8((uint16_t *)cptr, wrt.row_ctx(row), col, v);
+    }
+  }
+  // the next band overwrites this region: keep its writes behind the reads
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
 
 // ONEBUF: single LDS buffer (36 KB vs 72 KB) with a second barrier per
 // k-step — 4 workgroups/CU instead of 2 (16 waves/CU): trades one barrier

@@ -225,8 +225,12 @@ __global__ __launch_bounds__(512) void pipe256_gemm_k(
 // Per-thread glds counts HALVE (1 granule per stage): every counted
 // vmcnt is half the 8-wave kernel's. A/B gate: MPIAMD_P256X16.
 // ======================================================================
+// VEC: row-major epilogue (vec_epilogue_band, mix_gemm.h) through each
+// wave's own 8 KiB slice of the dead operand images: bf16 rows leave as
+// full 128-byte segments of the wave's 64 columns, fp32 as 256-byte ones.
+// Needs a VEC writer and no bias; chosen per launch by the launchers.
 template <bool C_F32, bool BIAS, int SWZ = 1, int SP = 1,
-          class WR = LinearWriter, bool USE_WR = false>
+          class WR = LinearWriter, bool USE_WR = false, bool VEC = false>
 __global__ __launch_bounds__(1024) void pipe256x16_gemm_k(
     const uint16_t *__restrict__ a, long lda, const uint16_t *__restrict__ b,
     long ldb, void *__restrict__ cptr, int M, int N, int K, long ldc,
@@ -325,6 +329,20 @@ __global__ __launch_bounds__(1024) void pipe256x16_gemm_k(
   if (SP == 1) __builtin_amdgcn_s_setprio(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
+  if constexpr (VEC) {
+    static_assert(!BIAS && WR::VEC, "vector epilogue: VEC writer, no bias");
+    WR vw = wrt;
+    if constexpr (!USE_WR) vw = WR{ldc};
+    __builtin_amdgcn_s_barrier(); // other waves' last operand reads
+    asm volatile("" ::: "memory");
+    char *wl = (char *)lds + wave * 8192;
+#pragma unroll
+    for (int mh = 0; mh < 2; ++mh)
+      vec_epilogue_band<2, C_F32>(vw, cptr, wl, acc[mh], lane,
+                                  row0 + wr * 64 + mh * 32, col0 + wc * 64, M,
+                                  N);
+    return;
+  }
 #pragma unroll
   for (int mh = 0; mh < 2; ++mh) {
 #pragma unroll
@@ -382,6 +400,19 @@ static hipError_t launch_pipe256_wr(const LA &la, const LB &lb, void *c,
   int cpx = (nwg % 8 == 0 && nwg >= 32) ? nwg / 8 : 0;
   constexpr int SWZ = 1, NPB = 1, SP = 1;
   if (use_p256x16()) {
+    if constexpr (WR::VEC) {
+      if (epilogue_vec_eligible(wrt, c, N, c_f32, 1, 0)) {
+        if (c_f32)
+          pipe256x16_gemm_k<true, false, SWZ, SP, WR, true, true>
+              <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
+                                    tiles_n, cpx, nullptr, wrt);
+        else
+          pipe256x16_gemm_k<false, false, SWZ, SP, WR, true, true>
+              <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
+                                    tiles_n, cpx, nullptr, wrt);
+        return hipGetLastError();
+      }
+    }
     if (c_f32)
       pipe256x16_gemm_k<true, false, SWZ, SP, WR, true><<<nwg, 1024, 0, s>>>(
           la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, nullptr,
@@ -413,6 +444,18 @@ static hipError_t launch_pipe256(const LA &la, const LB &lb, void *c, int M,
   // round-1 gemm256 (+44%); +17-42% on the real model shapes
   constexpr int SWZ = 1, NPB = 1, SP = 1;
   if (use_p256x16()) {
+    if (!bias &&
+        epilogue_vec_eligible(LinearWriter{ldc}, c, N, c_f32, 1, 0)) {
+      if (c_f32)
+        pipe256x16_gemm_k<true, false, SWZ, SP, LinearWriter, false, true>
+            <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
+                                  tiles_n, cpx, bias);
+      else
+        pipe256x16_gemm_k<false, false, SWZ, SP, LinearWriter, false, true>
+            <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
+                                  tiles_n, cpx, bias);
+      return hipGetLastError();
+    }
     if (c_f32) {
       if (bias)
         pipe256x16_gemm_k<true, true, SWZ, SP><<<nwg, 1024, 0, s>>>(

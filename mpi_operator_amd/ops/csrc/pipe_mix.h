@@ -765,7 +765,12 @@ template <class SRC> struct Tn8Pipe {
   }
 };
 
-template <class SA, class SB, bool C_F32, class WR>
+// VEC: row-major epilogue (vec_epilogue_band, mix_gemm.h) — one s_barrier
+// after the drain, then each wave transposes its two 32x32 fragments
+// through its own 8 KiB slice of the (now dead) operand images and issues
+// 16-byte stores; chosen per launch by launch_pipe_mix8_wr. VEC = false is
+// the one-element-per-lane epilogue, unchanged.
+template <class SA, class SB, bool C_F32, class WR, bool VEC = false>
 __global__ __launch_bounds__(512) void pipe_mix8_k(
     SA sa, SB sb, void *__restrict__ cptr, int M, int N, int K, WR wrt,
     int tiles_n, int kt_per_split, long split_stride, int xcd_cpx, int swap,
@@ -852,6 +857,19 @@ __global__ __launch_bounds__(512) void pipe_mix8_k(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
   cptr = (void *)((char *)cptr + split * split_stride * (C_F32 ? 4 : 2));
+  if constexpr (VEC) {
+    // every wave is past its last operand read (lgkmcnt(0) precedes the
+    // MFMAs) and its own glds (vmcnt(0) above) once it arrives here
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    char *wl = (char *)lds + wave * 8192;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+      vec_epilogue_band<1, C_F32>(wrt, cptr, wl + mi * 4096, &acc[mi], lane,
+                                  row0 + wr * 64 + mi * 32, col0 + wc * 32, M,
+                                  N);
+    return;
+  }
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
@@ -905,6 +923,17 @@ static hipError_t launch_pipe_mix8_wr(const SA8 &sa, const SB8 &sb, void *c,
   int cpx = (nwg % 8 == 0 && nwg >= 32 && (splits == 1 || use_sk_cpx()))
                 ? nwg / 8 : 0;
   dim3 grid(nwg, splits);
+  if constexpr (WR::VEC) {
+    if (epilogue_vec_eligible(wrt, c, N, c_f32, splits, split_stride)) {
+      if (c_f32)
+        pipe_mix8_k<SA8, SB8, true, WR, true><<<grid, 512, 0, s>>>(
+            sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, 0, zeros);
+      else
+        pipe_mix8_k<SA8, SB8, false, WR, true><<<grid, 512, 0, s>>>(
+            sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, 0, zeros);
+      return hipGetLastError();
+    }
+  }
   if (c_f32)
     pipe_mix8_k<SA8, SB8, true, WR><<<grid, 512, 0, s>>>(
         sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, 0, zeros);

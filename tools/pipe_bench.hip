@@ -1,6 +1,8 @@
 // Standalone harness for the deep-pipelined GEMM work (round 2):
 //   --probe   dump ds_read_b64_tr_b16 per-lane gather semantics (the HW
 //             transpose read planned for the TN-operand pipeline)
+//   --epi     scalar vs 16-byte-store epilogue timing at the ResNet101
+//             bs64 shapes (mix_gemm.h vec_epilogue_band)
 //   default   numerics check (CPU f64 ref at small sizes) + TF sweep of
 //             gemm256 (round-1) vs pipe256 swizzle/barrier variants at
 //             4096³/8192³ bf16 on uniform random [-1,1) operands
@@ -520,6 +522,59 @@ static int xcheck(int kind, long M, int N, int K, int splits) {
   return bad;
 }
 
+// ---- scalar vs 16-byte-store epilogue at the flagship's shapes (--epi) --
+// kind 0: NT×NT through launch_nt_gemm (1x1 conv forward; the route — 256²
+// or 128² pipe — is the library's own choice), kind 1: TN×TN (wgrad; the
+// 3x3 wgrad's gather is replaced by plain operands of the same GEMM shape).
+// Output bf16 when splits == 1, fp32 slabs otherwise, as in the model.
+// Each figure is the mean of `iters` back-to-back launches; scalar and
+// vector alternate over three rounds so drift shows as spread, not as gain.
+static void bench_epi(const char *name, int kind, int M, int N, int K,
+                      int splits, int iters) {
+  uint16_t *da, *db;
+  void *dc;
+  bool f32 = splits > 1;
+  CHECK(hipMalloc(&da, (long)M * K * 2));
+  CHECK(hipMalloc(&db, (long)N * K * 2));
+  CHECK(hipMalloc(&dc, (long)splits * M * N * (f32 ? 4 : 2)));
+  CHECK(hipMemset(da, 0x3c, (long)M * K * 2));
+  CHECK(hipMemset(db, 0x3c, (long)N * K * 2));
+  auto launch = [&]() -> hipError_t {
+    if (kind == 0) {
+      GemmLoader la{da, M, (long)K, K};
+      GemmLoader lb{db, N, (long)K, K};
+      return launch_nt_gemm(la, lb, dc, M, N, K, N, f32, 0, splits);
+    }
+    TnPipe<PlainTnSrc> sa{{da, (long)M, K, M}};
+    TnPipe<PlainTnSrc> sb{{db, (long)N, K, N}};
+    return launch_pipe_mix_wr(sa, sb, dc, M, N, K, LinearWriter{(long)N}, N,
+                              f32, 0, splits);
+  };
+  float us[2][3];
+  hipEvent_t e0, e1;
+  hipEventCreate(&e0); hipEventCreate(&e1);
+  for (int round = 0; round < 3; ++round)
+    for (int vec = 0; vec < 2; ++vec) {
+      g_epilogue_vec.store(vec != 0);
+      CHECK(launch()); // warm-up, also loads the code object
+      CHECK(hipDeviceSynchronize());
+      hipEventRecord(e0);
+      for (int i = 0; i < iters; ++i) launch();
+      hipEventRecord(e1);
+      CHECK(hipEventSynchronize(e1));
+      float ms;
+      hipEventElapsedTime(&ms, e0, e1);
+      us[vec][round] = ms * 1e3f / iters;
+    }
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  g_epilogue_vec.store(true);
+  printf("epi %-22s M%-6d N%-5d K%-6d sk%-2d %s  scalar %7.2f %7.2f %7.2f us"
+         "  vector %7.2f %7.2f %7.2f us\n", name, M, N, K, splits,
+         f32 ? "f32 " : "bf16", us[0][0], us[0][1], us[0][2], us[1][0],
+         us[1][1], us[1][2]);
+  hipFree(da); hipFree(db); hipFree(dc);
+}
+
 static int conv_splits_h(long M, int Ncols, int K) {
   long tiles = ((M + 127) / 128) * ((Ncols + 127) / 128);
   int nk = (K + 63) / 64;
@@ -620,6 +675,15 @@ int main(int argc, char **argv) {
     bad += xcheck(1, 64, 2048, 1000, 1);
     printf(bad ? "XCHECK FAILURES\n" : "xcheck all OK\n");
     return bad != 0;
+  }
+  if (argc > 1 && !strcmp(argv[1], "--epi")) {
+    // ResNet101 bs64 shapes (M, N, K as the GEMM sees them)
+    bench_epi("layer3 conv3 fwd", 0, 12544, 1024, 256, 1, 200);
+    bench_epi("layer3 conv1 fwd", 0, 12544, 256, 1024, 2, 200);
+    bench_epi("layer3 conv1 wgrad", 1, 256, 1024, 12544, 24, 200);
+    bench_epi("layer1 conv3 fwd", 0, 200704, 256, 64, 1, 100);
+    bench_epi("layer3 3x3 wgrad", 1, 256, 2304, 12544, 8, 200);
+    return 0;
   }
   if (argc > 1 && !strcmp(argv[1], "--tn-debug")) {
     run_tn_debug();
