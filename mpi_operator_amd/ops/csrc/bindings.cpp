@@ -67,6 +67,43 @@ void check_cl_bf16(const Tensor &t, const char *name) {
               name, " must be 4-D channels_last");
 }
 
+// The streaming NHWC kernels walk 16 B octets of 8 channels with pitch C/8:
+// a C that is no multiple of 8 would get a pitch-8 walk over garbage channels.
+void check_c8(const Tensor &t, const char *name) {
+  TORCH_CHECK(t.size(1) % 8 == 0 && t.size(1) >= 8, name,
+              ": channel count must be a positive multiple of 8, got ",
+              t.size(1));
+}
+
+void check_bn_c(const Tensor &t, const char *name) {
+  check_c8(t, name);
+  TORCH_CHECK(t.size(1) <= 2048, name, ": BatchNorm kernels need C <= 2048");
+  TORCH_CHECK(t.numel() > 0, name, " is empty");
+}
+
+// operand of an elementwise kernel that indexes it exactly like `like`
+void check_same_cl_bf16(const Tensor &t, const Tensor &like, const char *name) {
+  check_cl_bf16(t, name);
+  TORCH_CHECK(t.sizes() == like.sizes(), name, " has shape ", t.sizes(),
+              ", expected ", like.sizes());
+  TORCH_CHECK(t.device() == like.device(), name, " is on another device");
+}
+
+// per-channel fp32 vector ([C], dense) read by a kernel
+void check_chan_f32(const Tensor &t, int64_t C, const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                  t.is_contiguous() && t.numel() == C,
+              name, " must be a contiguous fp32 [C] GPU tensor");
+}
+
+// ReLU bitmask, one byte per octet: [M][C/8] uint8
+void check_relu_mask(const Tensor &t, int64_t octets, const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kByte &&
+                  t.is_contiguous() && t.numel() == octets,
+              name, " must be a contiguous uint8 GPU tensor of ", octets,
+              " bytes (one per 8 channels), got ", t.numel());
+}
+
 Tensor empty_cl_bf16(int64_t n, int64_t c, int64_t h, int64_t w, const Tensor &like) {
   // memory_format at allocation — .contiguous() on a fresh empty COPIES.
   return at::empty({n, c, h, w}, like.options().dtype(at::kBFloat16),
@@ -327,10 +364,15 @@ static Tensor conv2d_wgrad(const Tensor &x, const Tensor &dy, int64_t R,
   return dw;
 }
 
+static void check_ew_first(const Tensor &t, const char *name);
+static void check_ew_same(const Tensor &t, const Tensor &first,
+                          const char *name);
+
 // c = a + b, bf16 16B-vectorized (the residual-join gradient sum)
 static Tensor add_bf16_b(const Tensor &a, const Tensor &b) {
+  check_ew_first(a, "a");
+  check_ew_same(b, a, "b");
   const HIPDeviceGuard guard(a.device());
-  TORCH_CHECK(a.numel() == b.numel() && a.numel() % 8 == 0);
   Tensor c = at::empty_like(a);
   CHK(add_bf16(a.data_ptr(), b.data_ptr(), c.data_ptr(), a.numel(), cur_stream()));
   return c;
@@ -448,6 +490,7 @@ static std::vector<Tensor> bn_fwd_train_pre(
     const Tensor &beta, double eps, bool relu, const Tensor &running_mean,
     const Tensor &running_var, double momentum, const Tensor &res) {
   check_cl_bf16(x, "x");
+  check_bn_c(x, "x");
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   long M = (long)N * H * W;
@@ -463,7 +506,7 @@ static std::vector<Tensor> bn_fwd_train_pre(
   float *rv = rm ? running_var.data_ptr<float>() : nullptr;
   const void *resp = nullptr;
   if (res.defined() && res.numel() > 0) {
-    check_cl_bf16(res, "res");
+    check_same_cl_bf16(res, x, "res");
     resp = res.data_ptr();
   }
   Tensor mask;
@@ -489,20 +532,27 @@ static std::vector<Tensor> bn_fwd_train(const Tensor &x, const Tensor &gamma,
                                         const Tensor &running_var,
                                         double momentum, const Tensor &res) {
   check_cl_bf16(x, "x");
+  check_bn_c(x, "x");
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   long M = (long)N * H * W;
+  check_chan_f32(gamma, C, "gamma");
+  check_chan_f32(beta, C, "beta");
   auto f32 = x.options().dtype(at::kFloat);
   Tensor y = empty_cl_bf16(N, C, H, W, x);
   Tensor mean = at::empty({C}, f32), invstd = at::empty({C}, f32);
   Tensor scale = at::empty({C}, f32), shift = at::empty({C}, f32);
   Tensor partial = at::empty({(long)bn_grid_cap(C / 8) * 2 * C}, f32);
-  float *rm = running_mean.defined() && running_mean.numel() == C
-                  ? running_mean.data_ptr<float>() : nullptr;
-  float *rv = rm ? running_var.data_ptr<float>() : nullptr;
+  float *rm = nullptr, *rv = nullptr;
+  if (running_mean.defined() && running_mean.numel() > 0) {
+    check_chan_f32(running_mean, C, "running_mean");
+    check_chan_f32(running_var, C, "running_var");
+    rm = running_mean.data_ptr<float>();
+    rv = running_var.data_ptr<float>();
+  }
   const void *resp = nullptr;
   if (res.defined() && res.numel() > 0) {
-    check_cl_bf16(res, "res");
+    check_same_cl_bf16(res, x, "res");
     resp = res.data_ptr();
   }
   Tensor mask;
@@ -525,21 +575,47 @@ static std::vector<Tensor> bn_fwd_train(const Tensor &x, const Tensor &gamma,
 static Tensor bn_fwd_eval(const Tensor &x, const Tensor &scale,
                           const Tensor &shift, bool relu) {
   check_cl_bf16(x, "x");
+  check_bn_c(x, "x");
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  check_chan_f32(scale, C, "scale");
+  check_chan_f32(shift, C, "shift");
   Tensor y = empty_cl_bf16(N, C, H, W, x);
-  CHK(bn_fwd_eval_launch(x.data_ptr(), scale.contiguous().data_ptr<float>(),
-                         shift.contiguous().data_ptr<float>(), relu ? 1 : 0,
+  CHK(bn_fwd_eval_launch(x.data_ptr(), scale.data_ptr<float>(),
+                         shift.data_ptr<float>(), relu ? 1 : 0,
                          y.data_ptr(), (long)N * H * W, C, cur_stream()));
   return y;
+}
+
+// Operand checks shared by bn_bwd and bn_bwd_pre; returns the mask pointer
+// (nullptr: the kernels gate dy by y > 0 instead, and then read y).
+static const uint8_t *check_bn_bwd_args(const Tensor &dy, const Tensor &x,
+                                        const Tensor &y, const Tensor &gamma,
+                                        const Tensor &mean,
+                                        const Tensor &invstd, bool relu,
+                                        const Tensor &mask) {
+  check_cl_bf16(x, "x");
+  check_bn_c(x, "x");
+  check_same_cl_bf16(dy, x, "dy");
+  int64_t C = x.size(1);
+  check_chan_f32(gamma, C, "gamma");
+  check_chan_f32(mean, C, "mean");
+  check_chan_f32(invstd, C, "invstd");
+  const uint8_t *mp = nullptr;
+  if (mask.defined() && mask.numel() > 0) {
+    check_relu_mask(mask, x.numel() / 8, "mask");
+    mp = mask.data_ptr<uint8_t>();
+  }
+  if (relu && !mp) check_same_cl_bf16(y, x, "y");
+  return mp;
 }
 
 static std::vector<Tensor> bn_bwd(const Tensor &dy, const Tensor &x,
                                   const Tensor &y, const Tensor &gamma,
                                   const Tensor &mean, const Tensor &invstd,
                                   bool relu, const Tensor &mask) {
-  check_cl_bf16(dy, "dy");
-  check_cl_bf16(x, "x");
+  const uint8_t *mp =
+      check_bn_bwd_args(dy, x, y, gamma, mean, invstd, relu, mask);
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   long M = (long)N * H * W;
@@ -548,8 +624,6 @@ static std::vector<Tensor> bn_bwd(const Tensor &dy, const Tensor &x,
   Tensor dgamma = at::empty({C}, f32), dbeta = at::empty({C}, f32);
   Tensor k1 = at::empty({C}, f32), k2 = at::empty({C}, f32), k3 = at::empty({C}, f32);
   Tensor partial = at::empty({(long)bn_grid_cap(C / 8) * 2 * C}, f32);
-  const uint8_t *mp =
-      mask.defined() && mask.numel() > 0 ? mask.data_ptr<uint8_t>() : nullptr;
   CHK(bn_bwd_launch(dy.data_ptr(), x.data_ptr(), y.data_ptr(), mp,
                     gamma.data_ptr<float>(), mean.data_ptr<float>(),
                     invstd.data_ptr<float>(), relu ? 1 : 0, dx.data_ptr(),
@@ -566,20 +640,19 @@ static std::vector<Tensor> bn_bwd_pre(const Tensor &dy, const Tensor &slab,
                                       const Tensor &gamma, const Tensor &mean,
                                       const Tensor &invstd, bool relu,
                                       const Tensor &mask) {
-  check_cl_bf16(dy, "dy");
-  check_cl_bf16(x, "x");
+  const uint8_t *mp =
+      check_bn_bwd_args(dy, x, y, gamma, mean, invstd, relu, mask);
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   long M = (long)N * H * W;
-  TORCH_CHECK(slab.dim() == 3 && slab.size(0) >= 1 && slab.size(1) == 2 &&
-                  slab.size(2) == C && slab.is_contiguous() &&
-                  slab.scalar_type() == at::kFloat, "slab must be [rows][2][C] fp32");
+  TORCH_CHECK(slab.is_cuda() && slab.dim() == 3 && slab.size(0) >= 1 &&
+                  slab.size(1) == 2 && slab.size(2) == C &&
+                  slab.is_contiguous() && slab.scalar_type() == at::kFloat,
+              "slab must be [rows][2][C] fp32");
   auto f32 = x.options().dtype(at::kFloat);
   Tensor dx = empty_cl_bf16(N, C, H, W, x);
   Tensor dgamma = at::empty({C}, f32), dbeta = at::empty({C}, f32);
   Tensor k1 = at::empty({C}, f32), k2 = at::empty({C}, f32), k3 = at::empty({C}, f32);
-  const uint8_t *mp =
-      mask.defined() && mask.numel() > 0 ? mask.data_ptr<uint8_t>() : nullptr;
   CHK(bn_bwd_pre_launch(slab.data_ptr<float>(), (int)slab.size(0),
                         dy.data_ptr(), x.data_ptr(), y.data_ptr(), mp,
                         gamma.data_ptr<float>(), mean.data_ptr<float>(),
@@ -661,11 +734,22 @@ static std::vector<Tensor> join_bwd_stats(
 }
 
 // ------------------------- pooling -------------------------
+// the argmax byte holds r*K + s, so K*K must fit in a uint8
+static void check_pool_geom(int64_t K, int64_t stride, int64_t pad) {
+  TORCH_CHECK(K >= 1 && K <= 15 && stride >= 1 && pad >= 0 && pad < K,
+              "maxpool needs 1 <= K <= 15, stride >= 1, 0 <= pad < K; got K=",
+              K, " stride=", stride, " pad=", pad);
+}
+
 static std::vector<Tensor> maxpool_fwd(const Tensor &x, int64_t K,
                                        int64_t stride, int64_t pad) {
   check_cl_bf16(x, "x");
+  check_c8(x, "x");
+  check_pool_geom(K, stride, pad);
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(H + 2 * pad >= K && W + 2 * pad >= K,
+              "maxpool window larger than the padded input");
   int HO = (H + 2 * (int)pad - (int)K) / (int)stride + 1;
   int WO = (W + 2 * (int)pad - (int)K) / (int)stride + 1;
   Tensor y = empty_cl_bf16(N, C, HO, WO, x);
@@ -679,8 +763,20 @@ static std::vector<Tensor> maxpool_fwd(const Tensor &x, int64_t K,
 static Tensor maxpool_bwd(const Tensor &dy, const Tensor &idx, int64_t H,
                           int64_t W, int64_t K, int64_t stride, int64_t pad) {
   check_cl_bf16(dy, "dy");
+  check_c8(dy, "dy");
+  check_pool_geom(K, stride, pad);
   const HIPDeviceGuard guard(dy.device());
   int N = dy.size(0), C = dy.size(1), HO = dy.size(2), WO = dy.size(3);
+  TORCH_CHECK(H + 2 * pad >= K && W + 2 * pad >= K &&
+                  HO == (H + 2 * pad - K) / stride + 1 &&
+                  WO == (W + 2 * pad - K) / stride + 1,
+              "dy is not the pooled shape of an input of ", H, "x", W);
+  // idx is [N][HO][WO][C] uint8: one argmax byte per dy element
+  TORCH_CHECK(idx.is_cuda() && idx.device() == dy.device() &&
+                  idx.scalar_type() == at::kByte && idx.is_contiguous() &&
+                  idx.numel() == dy.numel(),
+              "idx must be a contiguous uint8 GPU tensor with one byte per "
+              "dy element");
   Tensor dx = empty_cl_bf16(N, C, H, W, dy);
   CHK(maxpool_bwd_launch(dy.data_ptr(), idx.data_ptr<uint8_t>(), dx.data_ptr(),
                          N, (int)H, (int)W, HO, WO, C, (int)K, (int)stride,
@@ -691,6 +787,8 @@ static Tensor maxpool_bwd(const Tensor &dy, const Tensor &idx, int64_t H,
 // ------------------------- gap -------------------------
 static Tensor gap_fwd_b(const Tensor &x) {
   check_cl_bf16(x, "x");
+  check_c8(x, "x");
+  TORCH_CHECK(x.size(2) * x.size(3) >= 1, "x has no pixels");
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   Tensor y = at::empty({N, C}, x.options());
@@ -700,6 +798,9 @@ static Tensor gap_fwd_b(const Tensor &x) {
 
 static Tensor gap_bwd_b(const Tensor &dy, int64_t H, int64_t W) {
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(dy.dim() == 2, "dy must be [N][C]");
+  check_c8(dy, "dy");
+  TORCH_CHECK(H >= 1 && W >= 1, "gap_bwd needs H, W >= 1");
   const HIPDeviceGuard guard(dy.device());
   Tensor dyc = dy.contiguous();
   int N = dy.size(0), C = dy.size(1);
@@ -1191,8 +1292,38 @@ static std::vector<Tensor> mlm_head_bwd(const Tensor &logits, int64_t V64,
 }
 
 // ------------------------- add-relu -------------------------
+// The elementwise kernels index every operand with one linear octet index:
+// all operands must be dense bf16 GPU tensors of one shape and one memory
+// layout, with a whole number of 8-element octets.
+static void check_ew_first(const Tensor &t, const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, name,
+              " must be a bf16 GPU tensor");
+  TORCH_CHECK(t.is_contiguous() ||
+                  (t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast)),
+              name, " must be contiguous or 4-D channels_last");
+  TORCH_CHECK(t.numel() % 8 == 0, name,
+              ": element count must be a multiple of 8, got ", t.numel());
+}
+
+static void check_ew_same(const Tensor &t, const Tensor &first,
+                          const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == first.device() &&
+                  t.scalar_type() == at::kBFloat16,
+              name, " must be a bf16 tensor on the first operand's GPU");
+  // size-1 dims make strides ambiguous, so compare formats, not strides
+  const bool cl = first.dim() == 4 &&
+                  first.is_contiguous(at::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(t.sizes() == first.sizes() &&
+                  (cl ? t.is_contiguous(at::MemoryFormat::ChannelsLast)
+                      : t.is_contiguous()),
+              name, " must have the first operand's shape and memory layout (",
+              first.sizes(), "), got ", t.sizes());
+}
+
 static Tensor add_relu_fwd_b(const Tensor &a, const Tensor &b) {
   check_cl_bf16(a, "a");
+  check_ew_first(a, "a");
+  check_ew_same(b, a, "b");
   const HIPDeviceGuard guard(a.device());
   Tensor y = at::empty_like(a);
   CHK(add_relu_fwd(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), cur_stream()));
@@ -1200,6 +1331,8 @@ static Tensor add_relu_fwd_b(const Tensor &a, const Tensor &b) {
 }
 
 static Tensor add_relu_bwd_b(const Tensor &dy, const Tensor &y) {
+  check_ew_first(dy, "dy");
+  check_ew_same(y, dy, "y");
   const HIPDeviceGuard guard(dy.device());
   Tensor dx = at::empty_like(dy);
   CHK(add_relu_bwd(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), dy.numel(), cur_stream()));
@@ -1208,9 +1341,10 @@ static Tensor add_relu_bwd_b(const Tensor &dy, const Tensor &y) {
 
 static Tensor add_relu_bwd_add_b(const Tensor &dy, const Tensor &y,
                                  const Tensor &dx0) {
+  check_ew_first(dy, "dy");
+  check_ew_same(y, dy, "y");
+  check_ew_same(dx0, dy, "dx0");
   const HIPDeviceGuard guard(dy.device());
-  TORCH_CHECK(dy.numel() == y.numel() && dy.numel() == dx0.numel() &&
-              dy.numel() % 8 == 0);
   Tensor out = at::empty_like(dx0);
   CHK(add_relu_bwd_add(dy.data_ptr(), y.data_ptr(), dx0.data_ptr(),
                        out.data_ptr(), dy.numel(), cur_stream()));
@@ -1221,10 +1355,10 @@ static Tensor add_relu_bwd_add_b(const Tensor &dy, const Tensor &y,
 // dx0 + dy·mask — drops the full y re-read
 static Tensor add_relu_bwd_add_mask_b(const Tensor &dy, const Tensor &mask,
                                       const Tensor &dx0) {
+  check_ew_first(dy, "dy");
+  check_ew_same(dx0, dy, "dx0");
+  check_relu_mask(mask, dy.numel() / 8, "mask");
   const HIPDeviceGuard guard(dy.device());
-  TORCH_CHECK(dy.numel() == dx0.numel() && dy.numel() % 8 == 0 &&
-              mask.numel() == dy.numel() / 8 &&
-              mask.scalar_type() == at::kByte);
   Tensor out = at::empty_like(dx0);
   CHK(add_relu_bwd_add_mask(dy.data_ptr(), mask.data_ptr(), dx0.data_ptr(),
                             out.data_ptr(), dy.numel(), cur_stream()));
