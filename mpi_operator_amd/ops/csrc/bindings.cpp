@@ -49,6 +49,25 @@ int conv_splits(long M, int Ncols, int K) {
   return s < 1 ? 1 : (int)s;
 }
 
+// split count of the implicit wgrad (reduce dim = output pixels M):
+// fill the chip (tiles×splits ≈ budget blocks = 2 WG/CU) but keep ≥8 k-tiles
+// per split so each block amortizes its pipeline prologue; a flat 1024
+// cap overshot mid shapes (b2 1x1 dw: 256 splits of nk=3 ran at 94 TF
+// vs 167 at 64 splits). The target-block budget was tuned on the 4-wave
+// pipeline (2 WG/CU); the 8-wave kernel fills at half the workgroups —
+// MPIAMD_WGRAD_BUDGET overrides for A/B (default 512)
+int wgrad_splits(int Kout, int RSC, long M) {
+  int tiles = ((Kout + 127) / 128) * ((RSC + 127) / 128);
+  int nk = (int)((M + 63) / 64);
+  int splits = std::max(wgrad_budget() / tiles, 1);
+  splits = std::min(splits, std::max(nk / 8, 1));
+  splits = std::min(splits, 256);
+  // multiple of 8 so the split-major grid keeps a panel's N-tile sharers
+  // on one XCD ((split + splits*tile) % 8 must not walk with tile)
+  if (splits >= 8) splits &= ~7;
+  return splits;
+}
+
 #define CHK(call)                                                              \
   do {                                                                         \
     hipError_t e_ = (call);                                                    \
@@ -102,6 +121,61 @@ void check_relu_mask(const Tensor &t, int64_t octets, const char *name) {
                   t.is_contiguous() && t.numel() == octets,
               name, " must be a contiguous uint8 GPU tensor of ", octets,
               " bytes (one per 8 channels), got ", t.numel());
+}
+
+// Geometry of one convolution as every conv entry point sees it: the input
+// side (N, C, H, W), the weight (wK, wC, R, S) and the output side (dN, Kout,
+// HO, WO). The kernels derive every address from these numbers alone and
+// trust them: operands are walked in 16 B octets of 8 channels (C and Kout
+// multiples of 8 — forward too: its split-K reduce walks M*Kout in float4
+// groups and drops a tail), batch / channel / spatial extents index both
+// tensors, and row counts are ints. An entry point that derives the output
+// side itself (forward) passes dN = N, Kout = wK and HO = WO = -1.
+struct ConvGeom {
+  int HO, WO;
+};
+ConvGeom check_conv_geometry(const char *op, bool dgrad, int64_t N, int64_t C,
+                             int64_t H, int64_t W, int64_t wK, int64_t wC,
+                             int64_t R, int64_t S, int64_t dN, int64_t Kout,
+                             int64_t HO, int64_t WO, int64_t stride,
+                             int64_t pad) {
+  if (dgrad) {
+    // conv_dgrad routes every stride != 1 to the parity-2 decomposition
+    // (conv.hip conv_dgrad_s2), which is stride-2-only by construction.
+    TORCH_CHECK(stride == 1 || stride == 2, op,
+                " supports stride 1 or 2 only, got ", stride);
+  } else {
+    TORCH_CHECK(stride >= 1 && stride <= 64, op,
+                ": stride must be in [1, 64], got ", stride);
+  }
+  TORCH_CHECK(pad >= 0 && pad <= 64, op, ": pad must be in [0, 64], got ", pad);
+  TORCH_CHECK(R >= 1 && S >= 1 && R * S <= 1024, op, ": kernel ", R, "x", S,
+              " out of range");
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, op, ": empty input ", N, "x", H, "x",
+              W);
+  TORCH_CHECK(C >= 8 && C % 8 == 0, op,
+              " requires C%8==0 (pad the stem input), got C=", C);
+  TORCH_CHECK(Kout >= 8 && Kout % 8 == 0, op,
+              " requires out-channels %8==0, got ", Kout);
+  TORCH_CHECK(wK == Kout && wC == C, op, ": conv channel mismatch, weight is [",
+              wK, "][", wC, "], expected [", Kout, "][", C, "]");
+  TORCH_CHECK(dN == N, op, ": batch mismatch, ", dN, " output images for ", N,
+              " input images");
+  TORCH_CHECK(H + 2 * pad >= R && W + 2 * pad >= S, op, ": kernel ", R, "x", S,
+              " larger than the padded input");
+  int64_t ho = (H + 2 * pad - R) / stride + 1;
+  int64_t wo = (W + 2 * pad - S) / stride + 1;
+  TORCH_CHECK((HO < 0 || HO == ho) && (WO < 0 || WO == wo), op, ": output is ",
+              HO, "x", WO, ", the geometry gives ", ho, "x", wo);
+  const int64_t lim = (int64_t)1 << 31;
+  TORCH_CHECK(N * H * W < lim && N * ho * wo < lim && R * S * C < lim &&
+                  R * S * Kout < lim,
+              op, ": GEMM extent does not fit an int");
+  return {(int)ho, (int)wo};
+}
+
+void check_same_device(const Tensor &t, const Tensor &like, const char *name) {
+  TORCH_CHECK(t.device() == like.device(), name, " is on another device");
 }
 
 Tensor empty_cl_bf16(int64_t n, int64_t c, int64_t h, int64_t w, const Tensor &like) {
@@ -275,13 +349,15 @@ static Tensor conv2d_fwd(const Tensor &x, const Tensor &w, int64_t stride,
                          int64_t pad) {
   check_cl_bf16(x, "x");
   check_cl_bf16(w, "w");
+  check_same_device(w, x, "w");
+  const ConvGeom g = check_conv_geometry(
+      "conv2d_fwd", false, x.size(0), x.size(1), x.size(2), x.size(3),
+      w.size(0), w.size(1), w.size(2), w.size(3), x.size(0), w.size(0), -1, -1,
+      stride, pad);
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   int Kout = w.size(0), R = w.size(2), S = w.size(3);
-  TORCH_CHECK(w.size(1) == C, "conv channel mismatch");
-  TORCH_CHECK(C % 8 == 0, "conv requires C%8==0 (pad the stem input)");
-  int HO = (H + 2 * (int)pad - R) / (int)stride + 1;
-  int WO = (W + 2 * (int)pad - S) / (int)stride + 1;
+  int HO = g.HO, WO = g.WO;
   Tensor y = empty_cl_bf16(N, Kout, HO, WO, x);
   long M = (long)N * HO * WO;
   int splits = conv_splits(M, Kout, R * S * C);
@@ -301,14 +377,13 @@ static Tensor conv2d_dgrad(const Tensor &dy, const Tensor &w, int64_t H,
                            int64_t W, int64_t stride, int64_t pad) {
   check_cl_bf16(dy, "dy");
   check_cl_bf16(w, "w");
+  check_same_device(w, dy, "w");
+  check_conv_geometry("conv2d_dgrad", true, dy.size(0), w.size(1), H, W,
+                      w.size(0), w.size(1), w.size(2), w.size(3), dy.size(0),
+                      dy.size(1), dy.size(2), dy.size(3), stride, pad);
   const HIPDeviceGuard guard(dy.device());
   int N = dy.size(0), Kout = dy.size(1), HO = dy.size(2), WO = dy.size(3);
   int C = w.size(1), R = w.size(2), S = w.size(3);
-  TORCH_CHECK(Kout % 8 == 0, "dgrad requires out-channels %8==0");
-  // conv_dgrad routes every stride != 1 to the parity-2 decomposition
-  // (conv.hip conv_dgrad_s2), which is stride-2-only by construction.
-  TORCH_CHECK(stride == 1 || stride == 2,
-              "conv2d_dgrad supports stride 1 or 2 only, got ", stride);
   Tensor dx = empty_cl_bf16(N, C, H, W, dy);
   long M = (long)N * H * W;
   int splits = stride == 1 ? conv_splits(M, C, R * S * Kout) : 1;
@@ -329,27 +404,16 @@ static Tensor conv2d_wgrad(const Tensor &x, const Tensor &dy, int64_t R,
                            int64_t S, int64_t stride, int64_t pad) {
   check_cl_bf16(x, "x");
   check_cl_bf16(dy, "dy");
+  check_same_device(dy, x, "dy");
+  check_conv_geometry("conv2d_wgrad", false, x.size(0), x.size(1), x.size(2),
+                      x.size(3), dy.size(1), x.size(1), R, S, dy.size(0),
+                      dy.size(1), dy.size(2), dy.size(3), stride, pad);
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   int Kout = dy.size(1), HO = dy.size(2), WO = dy.size(3);
   int RSC = (int)R * S * C;
-  int tiles = ((Kout + 127) / 128) * ((RSC + 127) / 128);
   long M = (long)N * HO * WO;
-  int nk = (int)((M + 63) / 64);
-  // fill the chip (tiles×splits ≈ 512 blocks = 2 WG/CU) but keep ≥8 k-tiles
-  // per split so each block amortizes its pipeline prologue; a flat 1024
-  // cap overshot mid shapes (b2 1x1 dw: 256 splits of nk=3 ran at 94 TF
-  // vs 167 at 64 splits)
-  // target-block budget was tuned on the 4-wave pipeline (2 WG/CU); the
-  // 8-wave kernel fills at half the workgroups — MPIAMD_WGRAD_BUDGET
-  // overrides for A/B (default 512)
-  const int budget = wgrad_budget();
-  int splits = std::max(budget / tiles, 1);
-  splits = std::min(splits, std::max(nk / 8, 1));
-  splits = std::min(splits, 256);
-  // multiple of 8 so the split-major grid keeps a panel's N-tile sharers
-  // on one XCD ((split + splits*tile) % 8 must not walk with tile)
-  if (splits >= 8) splits &= ~7;
+  int splits = wgrad_splits(Kout, RSC, M);
   Tensor partial = at::empty({(long)splits, (long)Kout, (long)RSC},
                              x.options().dtype(at::kFloat));
   // dw bf16 (fp32-accumulated in the split-K slabs, rounded once at the
@@ -383,8 +447,14 @@ static void conv2d_dgrad_acc(const Tensor &dy, const Tensor &w, Tensor &dx_acc) 
   check_cl_bf16(dy, "dy");
   check_cl_bf16(w, "w");
   check_cl_bf16(dx_acc, "dx_acc");
-  const HIPDeviceGuard guard(dy.device());
+  check_same_device(w, dy, "w");
+  check_same_device(dx_acc, dy, "dx_acc");
   TORCH_CHECK(w.size(2) == 1 && w.size(3) == 1, "acc dgrad is 1x1-only");
+  // 1x1 stride 1 pad 0: dx_acc is [N][C][HO][WO], every extent from dy / w
+  check_conv_geometry("conv2d_dgrad_acc", true, dx_acc.size(0), dx_acc.size(1),
+                      dx_acc.size(2), dx_acc.size(3), w.size(0), w.size(1), 1,
+                      1, dy.size(0), dy.size(1), dy.size(2), dy.size(3), 1, 0);
+  const HIPDeviceGuard guard(dy.device());
   long M = (long)dy.size(0) * dy.size(2) * dy.size(3);
   CHK(conv_dgrad_1x1_acc(dy.data_ptr(), w.data_ptr(), dx_acc.data_ptr(), M,
                          (int)w.size(1), (int)dy.size(1), cur_stream()));
@@ -407,23 +477,23 @@ static std::vector<Tensor> conv2d_fwd_bn(const Tensor &x, const Tensor &w,
                                          bool fuse_epilogue) {
   check_cl_bf16(x, "x");
   check_cl_bf16(w, "w");
+  check_same_device(w, x, "w");
+  const ConvGeom g = check_conv_geometry(
+      "conv2d_fwd_bn", false, x.size(0), x.size(1), x.size(2), x.size(3),
+      w.size(0), w.size(1), w.size(2), w.size(3), x.size(0), w.size(0), -1, -1,
+      stride, pad);
   const HIPDeviceGuard guard(x.device());
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   int Kout = w.size(0), R = w.size(2), S = w.size(3);
-  int HO = (H + 2 * (int)pad - R) / (int)stride + 1;
-  int WO = (W + 2 * (int)pad - S) / (int)stride + 1;
+  int HO = g.HO, WO = g.WO;
   long M = (long)N * HO * WO;
   int splits = conv_splits(M, Kout, R * S * C);
   auto f32 = x.options().dtype(at::kFloat);
-  long rows = Kout % 8 != 0 ? 0
-                            : conv_fwd_bn_rows(M, C, Kout, R, S, (int)stride,
-                                               (int)pad, splits);
+  long rows = conv_fwd_bn_rows(M, C, Kout, R, S, (int)stride, (int)pad, splits);
   if (rows == 0 || (splits > 1 ? !fuse_splitk : !fuse_epilogue)) {
     Tensor y = conv2d_fwd(x, w, stride, pad);
     return {y, at::empty({0}, f32)};
   }
-  TORCH_CHECK(w.size(1) == C, "conv channel mismatch");
-  TORCH_CHECK(C % 8 == 0, "conv requires C%8==0 (pad the stem input)");
   Tensor y = empty_cl_bf16(N, Kout, HO, WO, x);
   Tensor slab = at::empty({rows, 2, (long)Kout}, f32);
   Tensor partial;
@@ -449,15 +519,17 @@ static std::vector<Tensor> conv2d_dgrad_bn(
     const Tensor &invstd, bool relu, const Tensor &mask) {
   check_cl_bf16(dy, "dy");
   check_cl_bf16(w, "w");
+  check_same_device(w, dy, "w");
+  check_conv_geometry("conv2d_dgrad_bn", true, dy.size(0), w.size(1), H, W,
+                      w.size(0), w.size(1), w.size(2), w.size(3), dy.size(0),
+                      dy.size(1), dy.size(2), dy.size(3), stride, pad);
   const HIPDeviceGuard guard(dy.device());
   int N = dy.size(0), Kout = dy.size(1), HO = dy.size(2), WO = dy.size(3);
   int C = w.size(1), R = w.size(2), S = w.size(3);
   long M = (long)N * H * W;
   auto f32 = dy.options().dtype(at::kFloat);
   int splits = stride == 1 ? conv_splits(M, C, R * S * Kout) : 1;
-  long rows = (Kout % 8 != 0 || C % 8 != 0)
-                  ? 0
-                  : conv_dgrad_bn_rows(M, C, Kout, R, S, (int)stride, splits);
+  long rows = conv_dgrad_bn_rows(M, C, Kout, R, S, (int)stride, splits);
   if (rows == 0) return {conv2d_dgrad(dy, w, H, W, stride, pad), at::empty({0}, f32)};
   check_cl_bf16(bx, "bx");
   TORCH_CHECK(bx.size(0) == N && bx.size(1) == C && bx.size(2) == H &&
@@ -1595,6 +1667,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelubwd_wt_route", [](int M, int N, int K) {
     return gemm_gelubwd_wants_wt(M, N, K) != 0;
   });
+  // split counts as conv2d_fwd / conv2d_dgrad (reduce extent K, before the
+  // launcher's clamp to K's 64-deep tiles) and conv2d_wgrad resolve them
+  m.def("conv_splits", [](int64_t M, int Ncols, int K) {
+    return conv_splits((long)M, Ncols, K);
+  }, py::arg("M"), py::arg("Ncols"), py::arg("K"));
+  m.def("conv_wgrad_splits", [](int Kout, int RSC, int64_t M) {
+    return wgrad_splits(Kout, RSC, (long)M);
+  }, py::arg("Kout"), py::arg("RSC"), py::arg("M"));
   m.def("conv2d_fwd", &conv2d_fwd);
   m.def("conv2d_dgrad", &conv2d_dgrad);
   m.def("conv2d_fwd_bn", &conv2d_fwd_bn, py::arg("x"), py::arg("w"),

@@ -451,10 +451,17 @@ static hipError_t conv_dgrad_s2(const void *dy, const void *w, void *dx,
       for (int s = (pw + pad) & 1; s < S; s += 2) ntw++;
       if (nth > 0 && ntw > 0) n_live++;
     }
-  // n_live==1 (1x1 s2): the single parity's epilogue zero-fills its three
-  // sibling pixels (Stride2ZeroWriter) — no full-tensor memset pass.
-  if (n_live != 1 && n_live != 4) // exotic shapes: zero the dead parities
-    (void)hipMemsetAsync(dx, 0, (long)N * H * W * C * 2, strm);
+  // n_live==1 with live parity (0,0) (1x1 s2, even pad): the single
+  // parity's epilogue zero-fills its three sibling pixels at (h+1, w+1)
+  // (Stride2ZeroWriter) — no full-tensor memset pass. With an odd pad the
+  // live parity is (1,1) and its dead siblings lie at h-1 / w-1, which the
+  // writer does not reach (row 0 and column 0 stayed unwritten): that shape
+  // takes the memset like every other one with dead parities.
+  const bool zero_sib = n_live == 1 && (pad & 1) == 0;
+  if (!zero_sib && n_live != 4) { // exotic shapes: zero the dead parities
+    hipError_t e = hipMemsetAsync(dx, 0, (long)N * H * W * C * 2, strm);
+    if (e != hipSuccess) return e;
+  }
 
   for (int ph = 0; ph < 2; ++ph) {
     int H2 = (H - ph + 1) / 2;
@@ -487,7 +494,7 @@ static hipError_t conv_dgrad_s2(const void *dy, const void *w, void *dx,
         TnPipe<DgradWS2TnSrc> sb2{{(const uint16_t *)w, C, Kout, K,
                                    R * S * C, S, r_first, s_first, sa.nth,
                                    sa.ntw}};
-        if (n_live == 1) {
+        if (zero_sib) {
           Stride2ZeroWriter wrt{W2, H2, ph, pw, W, H, C};
           e = launch_pipe_mix_wr(sa2, sb2, dx, (int)M, C, K, wrt, C, false,
                                  strm);
@@ -496,7 +503,7 @@ static hipError_t conv_dgrad_s2(const void *dy, const void *w, void *dx,
           e = launch_pipe_mix_wr(sa2, sb2, dx, (int)M, C, K, wrt, C, false,
                                  strm);
         }
-      } else if (n_live == 1) {
+      } else if (zero_sib) {
         Stride2ZeroWriter wrt{W2, H2, ph, pw, W, H, C};
         e = launch_mix_gemm_wr(sa, TnStage<DgradWS2Tn>{lb}, dx, (int)M, C, K,
                                wrt, C, false, strm);

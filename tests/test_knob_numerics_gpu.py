@@ -18,7 +18,10 @@ Child time limit: with no knob set, the slowest child measured 8.2 s wall on
 an MI355X (the pipe8_0 node list, 25 nodes, which ran first and so carried
 the cold extension load; the other 21 took 3.8-5.7 s, of which about 3 s is
 interpreter start and imports). CHILD_TIMEOUT_S is about ten times the
-slowest, rounded up, to absorb a cold load and a busy machine.
+slowest, rounded up, to absorb a cold load and a busy machine. With the
+test_conv_edges nodes added (3 to 15 tiny cases per conv configuration) the
+slowest child measured 6.3 s (pipe8_0 again, now 40 nodes, first and cold);
+the other 21 took 3.8-5.4 s, so the limit stands.
 """
 import re
 import subprocess
@@ -57,6 +60,22 @@ def ragged(*shapes):
 CONV_ALL = [f"{_OPS}test_conv_fwd_dgrad_wgrad[geom{i}]" for i in range(5)]
 CONV_S2 = CONV_ALL[2:]
 WGRAD_GEMM = "tests/test_gemm_gpu.py::test_gemm_splitk_via_wgrad_path"
+_EDGE = "tests/test_conv_edges_gpu.py::"
+
+
+def edges(*names):
+    return [f"{_EDGE}test_conv_edges[{n}]" for n in names]
+
+
+# test_conv_edges (per-element fp64 bounds): every case that takes a gather
+# (not a plain 1x1 GEMM) in fwd, dgrad or wgrad; the stride-2 dgrad cases;
+# the cases whose fwd/dgrad k extent can split (2, 3 and 4 k-tiles, 18)
+EDGE_GATHER = edges("nonsq-3x3", "nonsq-3x3-s2", "k1x3", "k3x1", "k5x5",
+                    "k3x3-p0", "k3x3-p2", "k2x2-s2", "k1x3-s2", "splitk",
+                    "c24-k136", "s3", "wgrad-8way", "one-pixel-3x3")
+EDGE_S2 = edges("nonsq-3x3-s2", "k1x1-s2", "k1x1-s2-p1", "k2x2-s2", "k1x3-s2")
+EDGE_SPLITK = edges("splitk", "nonsq-3x3", "c24-k136")
+EDGE_ACC = _EDGE + "test_conv_dgrad_acc"
 LINEAR = _OPS + "test_linear_fwd_bwd"
 RAGGED_SMALL = ragged("512-1000-2048", "96-24-40", "256-3072-768", "32-2-768",
                       "64-10-64", "96-30-40")
@@ -88,25 +107,25 @@ NO_SPLIT_NODES = [LINEAR] + RAGGED_ALL + [CONV_ALL[2]]
 
 # configuration (a key of test_knob_routes.CONFIGS) -> node ids
 CASES = {
-    "pipe8_0": PIPE8_NODES,
+    "pipe8_0": PIPE8_NODES + EDGE_GATHER + [EDGE_ACC],
     "p256x16_0": BIG_GEMMS + [FFN256, UNSPLIT_256],
     "pipe_0": BIG_GEMMS,
     "gemm256_0": BIG_GEMMS,
     "pipent_0": gemm(2, 3) + [LINEAR],
-    "pipemix_0": PIPE8_NODES + [WGRAD_GEMM],
+    "pipemix_0": PIPE8_NODES + [WGRAD_GEMM] + EDGE_GATHER + [EDGE_ACC],
     "pipemix_0_glds_0": gemm(*range(8)) + [LINEAR],
     "pipemix_0_glds_0_onebuf": gemm(*range(8)) + [LINEAR],
     # split-major needs splits % 8 == 0: only the 16-slab linear dw engages
     # the swapped grid. The conv wgrad resolves to 2 splits here (2 tiles,
     # 16 k-tiles), so it checks that the knob leaves such a launch tile-major.
     "pipemix_0_splitmajor": ragged("8192-256-512") + [WGRAD_GEMM],
-    "pipegather_0": CONV_ALL + [WGRAD_GEMM],
-    "pipegather_wgrad_0": CONV_ALL + [WGRAD_GEMM],
-    "pipes2_0": CONV_S2,
-    "no_splitk": NO_SPLIT_NODES,
-    "forced_splitk": NO_SPLIT_NODES + CONV_ALL[:2] + CONV_ALL[3:],
-    "wgrad_budget_64": CONV_ALL + [WGRAD_GEMM],
-    "wgrad_budget_2048": CONV_ALL + [WGRAD_GEMM],
+    "pipegather_0": CONV_ALL + [WGRAD_GEMM] + EDGE_GATHER,
+    "pipegather_wgrad_0": CONV_ALL + [WGRAD_GEMM] + EDGE_GATHER,
+    "pipes2_0": CONV_S2 + EDGE_S2,
+    "no_splitk": NO_SPLIT_NODES + EDGE_SPLITK,
+    "forced_splitk": NO_SPLIT_NODES + CONV_ALL[:2] + CONV_ALL[3:] + EDGE_SPLITK,
+    "wgrad_budget_64": CONV_ALL + [WGRAD_GEMM] + EDGE_GATHER,
+    "wgrad_budget_2048": CONV_ALL + [WGRAD_GEMM] + EDGE_GATHER,
     "bn_grids_64": BN,
     "bn_grid_1": BN,
     "gelu_deriv_0": [FFN, FFN256, FFN256_BWD],
