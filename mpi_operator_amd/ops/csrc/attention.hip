@@ -23,6 +23,7 @@
 // qkv view before any transpose — the kernel does the head split itself);
 // ctx is [B, S, H·64] so the consumer (attn.out linear) needs no reshape.
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8a;
 typedef __attribute__((ext_vector_type(4))) float float4a;

@@ -6,6 +6,8 @@
 // Reference op being replaced: the external image's cuDNN BN+ReLU
 // (SURVEY.md §2.3 N7).
 #include "common.h"
+#include "knobs.h"
+#include "launchers.h"
 
 // Per-thread fixed channel-group ownership: thread t owns channel block
 // cb = t % C8 and row-lane t / C8 — consecutive lanes read consecutive
@@ -638,47 +640,15 @@ __global__ void bn_bwd_apply_k(const ushort8 *__restrict__ dy,
   }
 }
 
-// Partials grid cap: 512 measured best THREE times now — flat 1024 lost
-// 6.6%, and the channel-aware cap (up to 4096 bands for narrow layers)
-// lost 4.4% (3363 vs 3517 same-box) even with the bands finalize: the
-// deeper slab costs more in finalize reads + L2 pressure than the extra
-// partials parallelism buys. MPIAMD_BN_GRID overrides for A/Bs; bindings
-// size the slab with bn_grid_cap — keep them in sync.
-extern "C" int bn_grid_cap(int C8) {
-  static const long ovr = [] {
-    const char *e = getenv("MPIAMD_BN_GRID");
-    long v = e ? atol(e) : 0;
-    return (v >= 1 && v <= 8192) ? v : 0;
-  }();
-  (void)C8;
-  return ovr ? (int)ovr : 512;
-}
-
+// partials grid, capped by knobs.h bn_grid_cap()
 static void bn_geom(long M, int C8, int &grid, int &rows_per_block) {
   rows_per_block = 256 / C8;
   long g = (M + rows_per_block - 1) / rows_per_block;
-  long cap = bn_grid_cap(C8);
+  long cap = bn_grid_cap();
   grid = (int)(g > cap ? cap : (g < 1 ? 1 : g));
 }
 
-// cap 2048 measured best (3846-3854 vs 3833-3834 img/s at 4096, 3800
-// at 8192, four-sample same-box sweep); MPIAMD_BN_APPLY_GRID overrides
-static long bn_apply_grid_cap() {
-  static const long cap = [] {
-    const char *e = getenv("MPIAMD_BN_APPLY_GRID");
-    long v = e ? atol(e) : 0;
-    return (v >= 64 && v <= 16384) ? v : 2048L;
-  }();
-  return cap;
-}
-
-// route introspection (host only): [bn_grid, bn_apply_grid] caps as the
-// launchers in this TU resolve them
-extern "C" void bn_route_knobs(int *out) {
-  out[0] = bn_grid_cap(1);
-  out[1] = (int)bn_apply_grid_cap();
-}
-
+// apply-pass grid, capped by knobs.h bn_apply_grid_cap()
 static int bn_apply_grid(long M, int C8) {
   const long cap = bn_apply_grid_cap();
   int rpb = 256 / C8;

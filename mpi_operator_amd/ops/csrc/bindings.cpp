@@ -1,6 +1,8 @@
 // PyTorch bindings for the gfx950 kernels. The only TU that includes torch
-// headers — kernel TUs are pure HIP and are linked via the extern "C"
-// launchers declared below.
+// headers — kernel TUs are pure HIP and are reached through the extern "C"
+// launchers of launchers.h, the one declaration both sides compile against.
+// The MPIAMD_* knobs are the inline functions of knobs.h: route_info() and
+// the split heuristics here call the same functions the launchers call.
 #include <torch/extension.h>
 
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -9,34 +11,17 @@
 
 #include <vector>
 
+#include "knobs.h"
+#include "launchers.h"
+
 namespace {
 
 using at::Tensor;
 
 // Late-stage convs produce few 128x128 output tiles (7x7 spatial ~100
 // blocks on 256 CUs): split the reduce dim so fwd/dgrad fill the chip,
-// paying one fp32 slab + reduce pass.
-// MPIAMD_CONV_SPLITS=n (n >= 1) forces the conv fwd/dgrad split count;
-// -1 = the heuristic below.
-int conv_splits_force() {
-  static const int force = [] {
-    const char *e = getenv("MPIAMD_CONV_SPLITS");
-    return e ? atoi(e) : -1;
-  }();
-  return force >= 1 ? force : -1;
-}
-
-// target-block budget of the conv-wgrad split count (conv2d_wgrad);
-// MPIAMD_WGRAD_BUDGET overrides within [64, 2048] for A/B (default 512)
-int wgrad_budget() {
-  static const int budget = [] {
-    const char *e = getenv("MPIAMD_WGRAD_BUDGET");
-    int v = e ? atoi(e) : 0;
-    return (v >= 64 && v <= 2048) ? v : 512;
-  }();
-  return budget;
-}
-
+// paying one fp32 slab + reduce pass. knobs.h conv_splits_force()
+// (MPIAMD_CONV_SPLITS) overrides the heuristic.
 int conv_splits(long M, int Ncols, int K) {
   const int force = conv_splits_force();
   if (force >= 1) return force;
@@ -185,164 +170,6 @@ Tensor empty_cl_bf16(int64_t n, int64_t c, int64_t h, int64_t w, const Tensor &l
 }
 
 } // namespace
-
-// ---- extern "C" launchers from the .hip TUs ----
-extern "C" {
-// route introspection: each TU reports the knobs its own launchers resolve
-void gemm_route_knobs(int *);  // gemm.hip, 15 values
-int gemm_nt_route_id(int, int, int, int);
-int gemm_set_epilogue_vec(int); // gemm.hip: returns the previous value
-void conv_route_knobs(int *);  // conv.hip, 3 values
-void ln_route_knobs(int *);    // layernorm.hip, 2 values
-void bn_route_knobs(int *);    // batchnorm.hip, 2 values
-hipError_t add_relu_fwd(const void *, const void *, void *, long, hipStream_t);
-hipError_t add_bf16(const void *, const void *, void *, long, hipStream_t);
-hipError_t add_relu_bwd(const void *, const void *, void *, long, hipStream_t);
-hipError_t add_relu_bwd_add(const void *, const void *, const void *, void *,
-                            long, hipStream_t);
-hipError_t add_relu_bwd_add_mask(const void *, const void *, const void *,
-                                 void *, long, hipStream_t);
-hipError_t gap_fwd(const void *, void *, int, int, int, hipStream_t);
-hipError_t gap_bwd(const void *, void *, int, int, int, hipStream_t);
-hipError_t bias_add(void *, const float *, long, int, hipStream_t);
-hipError_t colsum_bf16(const void *, float *, float *, long, int, long, hipStream_t);
-int colsum_chunks(long, int);
-struct SgdDesc {
-  const void *grad;
-  float *master;
-  float *mom;
-  uint16_t *out;
-  long numel;
-};
-hipError_t sgd_step_launch(const SgdDesc *, int, int, float, float, float, int,
-                           hipStream_t);
-struct OptDesc {
-  const void *grad;
-  float *master;
-  float *m;
-  float *v;
-  uint16_t *out;
-  long numel;
-};
-int optim_block_count(const OptDesc *, int);
-hipError_t optim_tick_launch(float *, const float *, int, double, double,
-                             double, hipStream_t);
-hipError_t l2norm_partials_launch(const OptDesc *, int, int, float *, int,
-                                  hipStream_t);
-hipError_t adam_step_launch(const OptDesc *, int, int, const float *, double,
-                            double, double, double, int, hipStream_t);
-hipError_t lamb_step_launch(const OptDesc *, int, int, const float *, float *,
-                            float *, int, float *, int, double, double, double,
-                            double, int, hipStream_t);
-int bn_grid_cap(int);
-hipError_t bn_fwd_train_launch(const void *, const void *, const float *,
-                               const float *, float, int, void *, uint8_t *,
-                               float *, float *, float *, float *, float *,
-                               float *, float *, float, long, int,
-                               hipStream_t);
-hipError_t bn_fwd_eval_launch(const void *, const float *, const float *, int,
-                              void *, long, int, hipStream_t);
-hipError_t bn_bwd_launch(const void *, const void *, const void *,
-                         const uint8_t *, const float *, const float *,
-                         const float *, int, void *, float *, float *,
-                         float *, float *, float *, float *, long, int,
-                         hipStream_t);
-hipError_t maxpool_fwd_launch(const void *, void *, uint8_t *, int, int, int,
-                              int, int, int, int, int, int, hipStream_t);
-hipError_t maxpool_bwd_launch(const void *, const uint8_t *, void *, int, int,
-                              int, int, int, int, int, int, int, hipStream_t);
-hipError_t softmax_xent_fwd_launch(const void *, const long *, float *, float *,
-                                   int, int, hipStream_t);
-hipError_t masked_xent_fwd_launch(const void *, const long *, float *, float *,
-                                  int, int, long, long, hipStream_t);
-hipError_t masked_xent_bwd_launch(const void *, const long *, const float *,
-                                  const float *, const float *, void *, int,
-                                  int, long, long, hipStream_t);
-hipError_t attn_fwd_launch(const void *, void *, void *, const float *, int,
-                           int, int, float, hipStream_t);
-hipError_t attn_bwd_launch(const void *, const void *, const void *, void *,
-                           int, int, int, float, hipStream_t);
-hipError_t flash_attn_fwd_launch(const void *, void *, float *, const float *,
-                                 int, int, int, float, hipStream_t);
-hipError_t flash_attn_bwd_launch(const void *, const void *, const void *,
-                                 const float *, float *, const float *, void *,
-                                 int, int, int, float, hipStream_t);
-hipError_t softmax_xent_bwd_launch(const float *, const long *, void *, int,
-                                   int, const float *, hipStream_t);
-hipError_t gemm_nt(const void *, const void *, void *, int, int, int, long,
-                   long, long, int, hipStream_t);
-hipError_t gemm_nt_bias(const void *, const void *, const float *, void *,
-                        int, int, int, long, long, long, hipStream_t);
-hipError_t gemm_nt_bias_sk(const void *, const void *, const float *, float *,
-                           void *, int, int, int, long, long, long, int,
-                           hipStream_t);
-int gemm_fwd_splits(int, int, int);
-hipError_t gemm_nt_tn(const void *, const void *, void *, int, int, int, long,
-                      long, long, int, hipStream_t);
-hipError_t gemm_nt_tn_acc(const void *, const void *, void *, int, int, int,
-                          long, long, long, hipStream_t);
-hipError_t gemm_nt_gelu_bias(const void *, const void *, const float *,
-                             void *, void *, int, int, int, long, long, long,
-                             hipStream_t);
-hipError_t gemm_nt_tn_gelubwd(const void *, const void *, const void *,
-                              void *, int, int, int, long, long, long,
-                              void *, hipStream_t);
-int gemm_gelubwd_wants_wt(int, int, int);
-hipError_t gemm_tn_tn(const void *, const void *, void *, int, int, int, long,
-                      long, long, int, hipStream_t);
-int gemm_tn_tn_splits(int, int, int);
-hipError_t gemm_tn_tn_sk(const void *, const void *, float *, void *, int,
-                         int, int, long, long, long, int, int, hipStream_t);
-hipError_t gemm_nt_tn_sk(const void *, const void *, float *, void *, int,
-                         int, int, long, long, long, int, hipStream_t);
-int gemm_nt_tn_splits(int, int, int);
-hipError_t conv_fwd(const void *, const void *, void *, int, int, int, int,
-                    int, int, int, int, int, int, int, int, float *,
-                    hipStream_t);
-hipError_t conv_dgrad(const void *, const void *, void *, int, int, int, int,
-                      int, int, int, int, int, int, int, int, float *,
-                      hipStream_t);
-hipError_t conv_fwd_bn(const void *, const void *, void *, int, int, int,
-                       int, int, int, int, int, int, int, int, int, float *,
-                       float *, hipStream_t);
-int conv_fwd_bn_rows(long, int, int, int, int, int, int, int);
-int conv_dgrad_bn_rows(long, int, int, int, int, int, int);
-hipError_t conv_dgrad_bn(const void *, const void *, void *, int, int, int,
-                         int, int, int, int, int, int, int, int, float *,
-                         const void *, const void *, const uint8_t *,
-                         const float *, const float *, int, float *,
-                         hipStream_t);
-hipError_t bn_bwd_pre_launch(const float *, int, const void *, const void *,
-                             const void *, const uint8_t *, const float *,
-                             const float *, const float *, int, void *,
-                             float *, float *, float *, float *, float *, long,
-                             int, hipStream_t);
-int bn_stats_grid(long, int);
-hipError_t bn_join_stats_launch(const void *, const uint8_t *, const void *,
-                                void *, const uint8_t *, const void *,
-                                const float *, const float *, float *,
-                                const void *, const float *, const float *,
-                                float *, long, int, hipStream_t);
-hipError_t bn_fwd_train_pre_launch(const float *, int, const void *,
-                                   const void *, const float *, const float *,
-                                   float, int, void *, uint8_t *, float *,
-                                   float *, float *, float *, float *,
-                                   float *, float, long, int, hipStream_t);
-hipError_t conv_dgrad_1x1_acc(const void *, const void *, void *, long, int,
-                              int, hipStream_t);
-hipError_t conv_wgrad_implicit(const void *, const void *, float *, void *,
-                               int, int, int, int, int, int, int, int, int,
-                               int, int, int, int, hipStream_t);
-hipError_t mfma_probe(const void *, const void *, float *, hipStream_t);
-hipError_t ln_fwd(const void *, const float *, const float *, void *, float *,
-                  float *, long, int, float, hipStream_t);
-hipError_t ln_fwd_add(const void *, const void *, const float *,
-                      const float *, void *, void *, float *, float *, long,
-                      int, float, hipStream_t);
-hipError_t ln_bwd(const void *, const void *, const float *, const float *,
-                  const float *, void *, float *, float *, long, int, int *,
-                  hipStream_t);
-}
 
 // ------------------------- conv -------------------------
 static Tensor conv2d_fwd(const Tensor &x, const Tensor &w, int64_t stride,
@@ -614,7 +441,7 @@ static std::vector<Tensor> bn_fwd_train(const Tensor &x, const Tensor &gamma,
   Tensor y = empty_cl_bf16(N, C, H, W, x);
   Tensor mean = at::empty({C}, f32), invstd = at::empty({C}, f32);
   Tensor scale = at::empty({C}, f32), shift = at::empty({C}, f32);
-  Tensor partial = at::empty({(long)bn_grid_cap(C / 8) * 2 * C}, f32);
+  Tensor partial = at::empty({(long)bn_grid_cap() * 2 * C}, f32);
   float *rm = nullptr, *rv = nullptr;
   if (running_mean.defined() && running_mean.numel() > 0) {
     check_chan_f32(running_mean, C, "running_mean");
@@ -695,7 +522,7 @@ static std::vector<Tensor> bn_bwd(const Tensor &dy, const Tensor &x,
   Tensor dx = empty_cl_bf16(N, C, H, W, x);
   Tensor dgamma = at::empty({C}, f32), dbeta = at::empty({C}, f32);
   Tensor k1 = at::empty({C}, f32), k2 = at::empty({C}, f32), k3 = at::empty({C}, f32);
-  Tensor partial = at::empty({(long)bn_grid_cap(C / 8) * 2 * C}, f32);
+  Tensor partial = at::empty({(long)bn_grid_cap() * 2 * C}, f32);
   CHK(bn_bwd_launch(dy.data_ptr(), x.data_ptr(), y.data_ptr(), mp,
                     gamma.data_ptr<float>(), mean.data_ptr<float>(),
                     invstd.data_ptr<float>(), relu ? 1 : 0, dx.data_ptr(),
@@ -1610,37 +1437,33 @@ static Tensor gemm_nt_b(const Tensor &a, const Tensor &b, bool c_f32) {
 }
 
 // ------------------- route introspection (host only) -------------------
-// Resolved value of every C++ MPIAMD_* knob, reported by the TU whose
-// launchers read it (never a second getenv here). Touches no device.
+// Resolved value of every C++ MPIAMD_* knob: the knobs.h functions the
+// launchers themselves call (inline, so one static per process). Touches no
+// device.
 static py::dict route_info() {
-  int g[15], c[3], l[2], b[2];
-  gemm_route_knobs(g);
-  conv_route_knobs(c);
-  ln_route_knobs(l);
-  bn_route_knobs(b);
   py::dict d;
-  d["pipemix"] = g[0] != 0;
-  d["pipe8"] = g[1] != 0;
-  d["p256x16"] = g[2] != 0;
-  d["gemm256"] = g[3] != 0;
-  d["pipe"] = g[4] != 0;
-  d["pipent"] = g[5] != 0;
-  d["glds"] = g[6] != 0;
-  d["onebuf"] = g[7] != 0;
-  d["splitmajor"] = g[8] != 0;
-  d["sk_cpx"] = g[9] != 0;
-  d["fwd_sk"] = g[10] != 0;
-  d["dx_sk"] = g[11]; // -1 shape-aware default, 0 never, 1 always
-  d["linear_sk"] = g[12] != 0;
-  d["gelu_deriv"] = g[13] != 0;
-  d["gelubwd_wt"] = g[14] != 0;
-  d["pipegather"] = c[0] != 0;
-  d["pipegather_wgrad"] = c[1] != 0;
-  d["pipes2"] = c[2] != 0;
-  d["ln_spec"] = l[0] != 0;
-  d["ln2"] = l[1] != 0;
-  d["bn_grid"] = b[0];
-  d["bn_apply_grid"] = b[1];
+  d["pipemix"] = use_pipemix();
+  d["pipe8"] = use_pipe8();
+  d["p256x16"] = use_p256x16();
+  d["gemm256"] = use_gemm256();
+  d["pipe"] = use_pipe();
+  d["pipent"] = use_pipent();
+  d["glds"] = use_glds();
+  d["onebuf"] = use_onebuf();
+  d["splitmajor"] = use_splitmajor();
+  d["sk_cpx"] = use_sk_cpx();
+  d["fwd_sk"] = fwd_sk_on();
+  d["dx_sk"] = dx_sk_mode(); // -1 shape-aware default, 0 never, 1 always
+  d["linear_sk"] = linear_sk_on();
+  d["gelu_deriv"] = gelu_deriv_mode();
+  d["gelubwd_wt"] = gelubwd_wt_on();
+  d["pipegather"] = use_pipegather();
+  d["pipegather_wgrad"] = use_pipegather_wgrad();
+  d["pipes2"] = use_pipes2();
+  d["ln_spec"] = ln_spec();
+  d["ln2"] = ln2_mode();
+  d["bn_grid"] = bn_grid_cap();
+  d["bn_apply_grid"] = bn_apply_grid_cap();
   d["conv_splits_force"] = conv_splits_force(); // -1 = heuristic
   d["wgrad_budget"] = wgrad_budget();
   return d;

@@ -11,11 +11,9 @@
 // operands (wgrad's dy and implicit im2col, dgrad's weight) are transposed
 // in the LDS write pass — nothing is ever materialized or pre-transposed.
 // wgrad is split-K with exact fp32 partial slabs + a reduce kernel.
+#include "launchers.h"
 #include "mfma_tile.h"
 #include "mix_gemm.h"
-
-extern "C" hipError_t splitk_reduce(const float *, int, long, void *, int,
-                                    hipStream_t);
 
 // Custom NT stager for conv fwd: the 4 staged rows (output pixels) are
 // FIXED for the whole kernel, so their (n, ho, wo) decomposition is hoisted
@@ -207,8 +205,7 @@ static hipError_t conv_fwd_impl(const void *x, const void *w, void *y, int N,
                                 int *splits_out, hipStream_t strm) {
   long M = (long)N * HO * WO;
   int K = R * S * C;
-  int nk = (K + BK - 1) / BK;
-  if (splits > nk) splits = nk > 0 ? nk : 1;
+  splits = clamp_splits(splits, K, BK);
   if (splits_out) *splits_out = splits;
   void *out = splits > 1 ? (void *)partial : y;
   bool f32 = splits > 1;
@@ -255,14 +252,6 @@ extern "C" hipError_t conv_fwd(const void *x, const void *w, void *y, int N,
 // conv_fwd_bn_rows() tells the caller how many slab rows to allocate; 0
 // means this shape's route has no stats epilogue (the BK=32 256² kernel) and
 // the caller must take the unfused pair.
-extern "C" int bn_stats_grid(long M, int C);
-extern "C" hipError_t bn_reduce_stats_fwd_launch(const float *, int, void *,
-                                                 float *, long, int,
-                                                 hipStream_t);
-extern "C" hipError_t bn_reduce_stats_bwd_launch(
-    const float *, int, void *, const void *, const void *, const uint8_t *,
-    const float *, const float *, int, float *, long, int, hipStream_t);
-
 static bool conv_is_plain_1x1(int R, int S, int stride, int pad) {
   return R == 1 && S == 1 && stride == 1 && pad == 0;
 }
@@ -270,8 +259,7 @@ static bool conv_is_plain_1x1(int R, int S, int stride, int pad) {
 extern "C" int conv_fwd_bn_rows(long M, int C, int Kout, int R, int S,
                                 int stride, int pad, int splits) {
   int K = R * S * C;
-  int nk = (K + BK - 1) / BK;
-  if (splits > nk) splits = nk > 0 ? nk : 1;
+  splits = clamp_splits(splits, K, BK);
   if (splits > 1) return bn_stats_grid(M, Kout);
   if (conv_is_plain_1x1(R, S, stride, pad) &&
       nt_gemm_route((int)M, Kout, C, Kout, C, C, 1) == NT_256)
@@ -286,8 +274,7 @@ extern "C" hipError_t conv_fwd_bn(const void *x, const void *w, void *y,
                                   hipStream_t strm) {
   long M = (long)N * HO * WO;
   int K = R * S * C;
-  int nk = (K + BK - 1) / BK;
-  if (splits > nk) splits = nk > 0 ? nk : 1;
+  splits = clamp_splits(splits, K, BK);
   if (splits > 1) {
     int sp = splits;
     hipError_t e = conv_fwd_impl(x, w, y, N, H, W, C, Kout, R, S, stride, pad,
@@ -342,17 +329,8 @@ extern "C" hipError_t conv_fwd_bn(const void *x, const void *w, void *y,
 extern "C" hipError_t conv_dgrad_1x1_acc(const void *dy, const void *w,
                                          void *dx_acc, long M, int C, int Kout,
                                          hipStream_t strm) {
-  if (use_pipemix()) {
-    NtPipe<PlainNtSrc> sa{{(const uint16_t *)dy, (long)Kout, (int)M, Kout}};
-    TnPipe<PlainTnSrc> sb{{(const uint16_t *)w, (long)C, Kout, C}};
-    return launch_pipe_mix_wr(sa, sb, dx_acc, (int)M, C, Kout,
-                              LinearAccWriter{(long)C}, C, false, strm);
-  }
-  GemmLoader la{(const uint16_t *)dy, (int)M, (long)Kout, Kout};
-  TnRowMajor lb{(const uint16_t *)w, (long)C, Kout, C};
-  return launch_mix_gemm_wr(NtStage<GemmLoader>{la}, TnStage<TnRowMajor>{lb},
-                            dx_acc, (int)M, C, Kout, LinearAccWriter{(long)C},
-                            C, false, strm);
+  return launch_nt_tn_gemm(use_pipemix(), dy, w, dx_acc, (int)M, C, Kout, Kout,
+                           C, LinearAccWriter{(long)C}, C, false, strm);
 }
 
 struct DgradWTn {
@@ -529,25 +507,15 @@ static hipError_t conv_dgrad_impl(const void *dy, const void *w, void *dx,
   int K = R * S * Kout;
   if (stride != 1)
     return conv_dgrad_s2(dy, w, dx, N, H, W, C, Kout, R, S, pad, HO, WO, strm);
-  int nk = (K + BK - 1) / BK;
-  if (splits > nk) splits = nk > 0 ? nk : 1;
+  splits = clamp_splits(splits, K, BK);
   if (splits_out) *splits_out = splits;
   void *out = splits > 1 ? (void *)partial : dx;
   bool f32 = splits > 1;
   hipError_t e;
   if (R == 1 && S == 1 && pad == 0) {
     // 1x1 dgrad: dx[M][C] = dy[M][Q] · w[Q][C] (w TN via tr_b16 pipeline)
-    if (use_pipemix()) {
-      NtPipe<PlainNtSrc> sa{{(const uint16_t *)dy, (long)Kout, (int)M, Kout}};
-      TnPipe<PlainTnSrc> sb{{(const uint16_t *)w, (long)C, Kout, C}};
-      e = launch_pipe_mix_wr(sa, sb, out, (int)M, C, Kout, LinearWriter{(long)C},
-                             C, f32, strm, splits);
-    } else {
-      GemmLoader la{(const uint16_t *)dy, (int)M, (long)Kout, Kout};
-      TnRowMajor lb{(const uint16_t *)w, (long)C, Kout, C};
-      e = launch_mix_gemm(NtStage<GemmLoader>{la}, TnStage<TnRowMajor>{lb}, out,
-                          (int)M, C, Kout, C, f32, strm, splits);
-    }
+    e = launch_nt_tn_gemm(use_pipemix(), dy, w, out, (int)M, C, Kout, Kout, C,
+                          LinearWriter{(long)C}, C, f32, strm, splits);
   } else if (use_pipegather()) {
     NtPipe<ConvDgradSrc<1>> sa{
         {(const uint16_t *)dy, H, W, Kout, HO, WO, S, pad, K, M}};
@@ -580,8 +548,7 @@ extern "C" hipError_t conv_dgrad(const void *dy, const void *w, void *dx,
 extern "C" int conv_dgrad_bn_rows(long M, int C, int Kout, int R, int S,
                                   int stride, int splits) {
   int K = R * S * Kout;
-  int nk = (K + BK - 1) / BK;
-  if (splits > nk) splits = nk > 0 ? nk : 1;
+  splits = clamp_splits(splits, K, BK);
   if (stride != 1 || splits <= 1) return 0;
   return bn_stats_grid(M, C);
 }
@@ -738,23 +705,16 @@ extern "C" hipError_t conv_wgrad_implicit(const void *dy, const void *x,
                                           hipStream_t strm) {
   long M = (long)N * HO * WO;
   int RSC = R * S * C;
-  int nk = (int)((M + BK - 1) / BK);
-  if (splits > nk) splits = nk > 0 ? nk : 1; // must match the launch's clamp:
-  // the reduce below must sum exactly the slabs the GEMM wrote.
+  // the launch's own clamp: the reduce below must sum exactly the slabs
+  // the GEMM wrote
+  splits = clamp_splits(splits, M, BK);
   TnRowMajor la{(const uint16_t *)dy, Kout, (int)M, Kout};
   hipError_t e;
   if (R == 1 && S == 1 && stride == 1 && pad == 0) {
     // 1x1 wgrad: the im2col column of x IS x itself — plain TN view
-    if (use_pipemix()) {
-      TnPipe<PlainTnSrc> sa{{(const uint16_t *)dy, (long)Kout, (int)M, Kout}};
-      TnPipe<PlainTnSrc> sb{{(const uint16_t *)x, (long)C, (int)M, C}};
-      e = launch_pipe_mix_wr(sa, sb, partial, Kout, RSC, (int)M,
-                             LinearWriter{(long)RSC}, RSC, true, strm, splits);
-    } else {
-      TnRowMajor lb{(const uint16_t *)x, (long)C, (int)M, C};
-      e = launch_mix_gemm(TnStage<TnRowMajor>{la}, TnStage<TnRowMajor>{lb},
-                          partial, Kout, RSC, (int)M, RSC, true, strm, splits);
-    }
+    e = launch_tn_tn_gemm(use_pipemix(), dy, x, partial, Kout, RSC, (int)M,
+                          Kout, C, LinearWriter{(long)RSC}, RSC, true, strm,
+                          splits);
   } else if (use_pipegather_wgrad()) {
     TnPipe<PlainTnSrc> sa{{(const uint16_t *)dy, (long)Kout, (int)M, Kout}};
     TnPipe<XcolSrc> sb{
@@ -768,13 +728,4 @@ extern "C" hipError_t conv_wgrad_implicit(const void *dy, const void *x,
   }
   if (e != hipSuccess) return e;
   return splitk_reduce(partial, splits, (long)Kout * RSC, dw, dw_bf16, strm);
-}
-
-// ---- route introspection (host only; tests/test_knob_routes.py) ----------
-// The gather gates as THIS TU's conv launchers resolve them: fwd/dgrad
-// gather, wgrad gather, stride-2 dgrad parity GEMMs.
-extern "C" void conv_route_knobs(int *out) {
-  out[0] = use_pipegather();
-  out[1] = use_pipegather_wgrad();
-  out[2] = use_pipes2();
 }

@@ -3,6 +3,7 @@
 // All memory-bound: vectorized 16 B/lane bf16 accesses (guide G13),
 // grid-stride with capped grids (guide G11).
 #include "common.h"
+#include "launchers.h"
 
 static inline int ew_grid(long lane_tasks, int block = 256) {
   long blocks = (lane_tasks + block - 1) / block;
@@ -224,14 +225,6 @@ extern "C" hipError_t gap_bwd(const void *dy, void *dx, int N, int HW, int C,
 constexpr int SGD_MAX_T = 40;
 constexpr int SGD_BLOCK = 256;
 constexpr int SGD_EPB = SGD_BLOCK * 32; // elements per block (8192)
-
-struct SgdDesc {
-  const void *grad;
-  float *master;
-  float *mom;
-  uint16_t *out; // nullptr if the param itself is fp32 (master IS the param)
-  long numel;
-};
 
 struct SgdArgs {
   SgdDesc d[SGD_MAX_T];
@@ -488,12 +481,6 @@ extern "C" int colsum_chunks(long M, int N) {
   if (gx < 1) gx = 1;
   return (int)gx;
 }
-
-extern "C" hipError_t splitk_reduce(const float *partial, int splits, long len,
-                                    void *out, int out_bf16,
-                                    hipStream_t s); // conv.hip
-extern "C" hipError_t slab_colreduce(const float *, float *, int, long,
-                                     hipStream_t); // conv.hip
 
 extern "C" hipError_t colsum_bf16(const void *dy, float *partial, float *db,
                                   long M, int N, long ld, hipStream_t s) {

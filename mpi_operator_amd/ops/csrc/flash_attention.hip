@@ -27,6 +27,7 @@
 // Layouts: qkv / dqkv [B, S, 3, H, 64]; ctx / dctx [B, S, H·64];
 // lse / delta [B, H, S] fp32; mask [B, S] fp32 additive (or nullptr).
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8a;
 typedef __attribute__((ext_vector_type(16))) float float16a;

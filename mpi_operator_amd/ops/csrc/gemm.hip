@@ -1,14 +1,9 @@
 // GEMM entry points over the MFMA tile templates: NT (both operands
 // k-contiguous), NT×TN and TN×TN (k-strided operands transposed in the LDS
 // write pass — linear backward runs with zero materialized transposes).
+#include "launchers.h"
 #include "mfma_tile.h"
 #include "mix_gemm.h"
-
-extern "C" hipError_t splitk_reduce(const float *, int, long, void *, int,
-                                    hipStream_t); // conv.hip
-extern "C" hipError_t splitk_bias_reduce(const float *, int, long, int,
-                                         const float *, void *,
-                                         hipStream_t); // conv.hip
 
 // A TN operand's 16-B column granules may overread up to 7 elements past
 // its `dim` columns; safe when the dim is %8, or when the ROW STRIDE is %8
@@ -37,19 +32,7 @@ extern "C" hipError_t gemm_nt_bias(const void *a, const void *b,
   return launch_nt_gemm(la, lb, c, M, N, K, ldc, false, s, 1, bias);
 }
 
-// Forward split-K (fc2-class M=4096/N=1024 shapes give 256 pipe-mix
-// workgroups = exactly 1/CU, half the block slots idle; deep K amortizes
-// the fp32 slab + bias-reduce pass). Measured same-box +0.7% on BERT-Large
-// bs32 (1372 -> 1381): default ON, MPIAMD_FWD_SK=0 disables. Heuristic
-// shared with the dw path.
-extern "C" int gemm_tn_tn_splits(int M, int N, int K); // below
-static bool fwd_sk_on() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_FWD_SK");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
+// Forward split-K (knobs.h fwd_sk_on): the dw heuristic, capped at 4.
 extern "C" int gemm_fwd_splits(int M, int N, int K) {
   if (!fwd_sk_on() || N % 8) return 1;
   int sp = gemm_tn_tn_splits(M, N, K);
@@ -73,17 +56,7 @@ extern "C" hipError_t gemm_nt_bias_sk(const void *a, const void *b,
 
 // FFN fc1 fused forward: g = gelu(x·w1ᵀ + b); the epilogue also saves
 // gelu'(h) (bf16, layout of C) so the backward epilogue is exp-free
-// (GeluBiasWriter). Both operands NT k-contiguous.
-// MPIAMD_GELU_DERIV (default 1): fwd saves gelu'(h) so bwd is exp-free;
-// =0 restores the save-pre/recompute-tanh pair for A/B.
-static bool gelu_deriv_mode() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_GELU_DERIV");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
+// (GeluBiasWriter; knobs.h gelu_deriv_mode). Both operands NT k-contiguous.
 template <class WR>
 static hipError_t gelu_fwd_route(WR wrt, const void *x, const void *w, void *g,
                                  int M, int N, int K, long lda, long ldb,
@@ -112,17 +85,6 @@ extern "C" hipError_t gemm_nt_gelu_bias(const void *x, const void *w,
                           g, M, N, K, lda, ldb, ldc, s);
   return gelu_fwd_route(GeluBiasPreWriter{ldc, bias, (uint16_t *)deriv}, x, w,
                         g, M, N, K, lda, ldb, ldc, s);
-}
-
-extern "C" hipError_t transpose2d_bf16(const void *, void *, int, int, long,
-                                       hipStream_t); // defined below
-
-static bool gelubwd_wt_on() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_GELUBWD_WT");
-    return e && e[0] == '1';
-  }();
-  return on;
 }
 
 // fc2-dx takes the transpose-plus-pipe256 route (below) iff this holds:
@@ -154,15 +116,8 @@ static hipError_t gelubwd_route(WR wrt, const void *dy, const void *w,
     GemmLoader lb{(const uint16_t *)wt_buf, N, K, K};
     return launch_pipe256_wr(la, lb, dh, M, N, K, ldc, false, wrt, s);
   }
-  if (use_pipemix() && N % 8 == 0) {
-    NtPipe<PlainNtSrc> sa{{(const uint16_t *)dy, lda, M, K}};
-    TnPipe<PlainTnSrc> sb{{(const uint16_t *)w, ldb, K, N}};
-    return launch_pipe_mix_wr(sa, sb, dh, M, N, K, wrt, ldc, false, s);
-  }
-  GemmLoader la{(const uint16_t *)dy, M, lda, K};
-  TnRowMajor lb{(const uint16_t *)w, ldb, K, N};
-  return launch_mix_gemm_wr(NtStage<GemmLoader>{la}, TnStage<TnRowMajor>{lb},
-                            dh, M, N, K, wrt, ldc, false, s);
+  return launch_nt_tn_gemm(use_pipemix() && N % 8 == 0, dy, w, dh, M, N, K,
+                           lda, ldb, wrt, ldc, false, s);
 }
 
 // wt_buf: optional [N][K] bf16 scratch enabling the transpose+pipe256
@@ -191,16 +146,8 @@ extern "C" hipError_t gemm_nt_tn_gelubwd(const void *dy, const void *w,
 extern "C" hipError_t gemm_nt_tn_acc(const void *a, const void *b, void *c,
                                      int M, int N, int K, long lda, long ldb,
                                      long ldc, hipStream_t s) {
-  if (use_pipemix() && tn_cols_ok(N, ldb)) {
-    NtPipe<PlainNtSrc> sa{{(const uint16_t *)a, lda, M, K}};
-    TnPipe<PlainTnSrc> sb{{(const uint16_t *)b, ldb, K, N}};
-    return launch_pipe_mix_wr(sa, sb, c, M, N, K, LinearAccWriter{ldc}, ldc,
-                              false, s);
-  }
-  GemmLoader la{(const uint16_t *)a, M, lda, K};
-  TnRowMajor lb{(const uint16_t *)b, ldb, K, N};
-  return launch_mix_gemm_wr(NtStage<GemmLoader>{la}, TnStage<TnRowMajor>{lb},
-                            c, M, N, K, LinearAccWriter{ldc}, ldc, false, s);
+  return launch_nt_tn_gemm(use_pipemix() && tn_cols_ok(N, ldb), a, b, c, M, N,
+                           K, lda, ldb, LinearAccWriter{ldc}, ldc, false, s);
 }
 
 // C[M][N] = A[M][K-contig] · B(k-strided [K rows][N cols])  — linear dx
@@ -210,36 +157,15 @@ extern "C" hipError_t gemm_nt_tn(const void *a, const void *b, void *c, int M,
   // pipe TN staging loads 16-B column granules: a cols%8!=0 operand would
   // read past the allocation on its last k-row (BERT vocab 30522 class) —
   // those shapes keep the elementwise-tail mix path
-  if (use_pipemix() && tn_cols_ok(N, ldb)) {
-    NtPipe<PlainNtSrc> sa{{(const uint16_t *)a, lda, M, K}};
-    TnPipe<PlainTnSrc> sb{{(const uint16_t *)b, ldb, K, N}};
-    return launch_pipe_mix_wr(sa, sb, c, M, N, K, LinearWriter{ldc}, ldc,
-                              c_f32 != 0, s);
-  }
-  GemmLoader la{(const uint16_t *)a, M, lda, K};
-  TnRowMajor lb{(const uint16_t *)b, ldb, K, N};
-  return launch_mix_gemm(NtStage<GemmLoader>{la}, TnStage<TnRowMajor>{lb}, c,
-                         M, N, K, ldc, c_f32 != 0, s);
+  return launch_nt_tn_gemm(use_pipemix() && tn_cols_ok(N, ldb), a, b, c, M, N,
+                           K, lda, ldb, LinearWriter{ldc}, ldc, c_f32 != 0, s);
 }
 
 // split-K form (small-batch dx underfills the chip, e.g. BERT bs=8:
 // dx[1024][4096] = 64 workgroups with K_reduce up to 4096): fp32 slabs in
-// `partial` reduced into bf16 C. Same splits heuristic as the dw path.
-extern "C" int gemm_tn_tn_splits(int M, int N, int K); // defined below
-
-// dx split-K, SHAPE-aware after three verdict flips: under the 8-wave
-// pipeline a 256-workgroup dx grid fills the chip and the slab+reduce tax
-// loses (bs32: 1542 with splits vs 1553 without), but SMALL grids still
-// need it badly (bs8's 64-wg dx: 690 with splits vs 614 without; so does
-// bert-base's 192-wg grid). Split only when tiles < 256.
-// MPIAMD_DX_SK: 0 = never split, 1 = always use the dw heuristic.
-static int dx_sk_mode() { // -1 = shape-aware default
-  static const int mode = [] {
-    const char *e = getenv("MPIAMD_DX_SK");
-    return e ? (e[0] == '1' ? 1 : 0) : -1;
-  }();
-  return mode;
-}
+// `partial` reduced into bf16 C. Same splits heuristic as the dw path,
+// gated by knobs.h dx_sk_mode (-1 = shape-aware: split only when
+// tiles < 256).
 extern "C" int gemm_nt_tn_splits(int M, int N, int K) {
   const int mode = dx_sk_mode();
   if (mode == 0) return 1;
@@ -252,27 +178,18 @@ extern "C" hipError_t gemm_nt_tn_sk(const void *a, const void *b,
                                     float *partial, void *c, int M, int N,
                                     int K, long lda, long ldb, long ldc,
                                     int splits, hipStream_t s) {
-  if (use_pipemix() && tn_cols_ok(N, ldb)) {
-    NtPipe<PlainNtSrc> sa{{(const uint16_t *)a, lda, M, K}};
-    TnPipe<PlainTnSrc> sb{{(const uint16_t *)b, ldb, K, N}};
-    if (splits <= 1)
-      return launch_pipe_mix_wr(sa, sb, c, M, N, K, LinearWriter{ldc}, ldc,
-                                false, s);
-    hipError_t e = launch_pipe_mix_wr(sa, sb, partial, M, N, K,
-                                      LinearWriter{ldc}, ldc, true, s, splits);
-    if (e != hipSuccess) return e;
-    return splitk_reduce(partial, splits, (long)M * ldc, c, 1, s);
-  }
-  GemmLoader la{(const uint16_t *)a, M, lda, K};
-  TnRowMajor lb{(const uint16_t *)b, ldb, K, N};
-  if (splits <= 1)
-    return launch_mix_gemm(NtStage<GemmLoader>{la}, TnStage<TnRowMajor>{lb},
-                           c, M, N, K, ldc, false, s);
-  hipError_t e =
-      launch_mix_gemm(NtStage<GemmLoader>{la}, TnStage<TnRowMajor>{lb},
-                      partial, M, N, K, ldc, true, s, splits);
-  if (e != hipSuccess) return e;
-  return splitk_reduce(partial, splits, (long)M * ldc, c, 1, s);
+  const bool pipe_ok = use_pipemix() && tn_cols_ok(N, ldb);
+  return launch_splitk(
+      [&](void *out, bool f32, int sp) {
+        return launch_nt_tn_gemm(pipe_ok, a, b, out, M, N, K, lda, ldb,
+                                 LinearWriter{ldc}, ldc, f32, s, sp);
+      },
+      partial, c, (long)M * ldc, splits, 1, s);
+}
+
+// TN×TN takes the pipe only when BOTH operands are granule-readable
+static bool tn_tn_pipe_ok(int M, int N, long lda, long ldb) {
+  return use_pipemix() && tn_cols_ok(M, lda) && tn_cols_ok(N, ldb);
 }
 
 // C[M][N] = Σ_k A(k-strided rows, M cols) · B(k-strided rows, N cols)
@@ -280,29 +197,14 @@ extern "C" hipError_t gemm_nt_tn_sk(const void *a, const void *b,
 extern "C" hipError_t gemm_tn_tn(const void *a, const void *b, void *c, int M,
                                  int N, int K, long lda, long ldb, long ldc,
                                  int c_f32, hipStream_t s) {
-  if (use_pipemix() && tn_cols_ok(M, lda) && tn_cols_ok(N, ldb)) {
-    TnPipe<PlainTnSrc> sa{{(const uint16_t *)a, lda, K, M}};
-    TnPipe<PlainTnSrc> sb{{(const uint16_t *)b, ldb, K, N}};
-    return launch_pipe_mix_wr(sa, sb, c, M, N, K, LinearWriter{ldc}, ldc,
-                              c_f32 != 0, s);
-  }
-  TnRowMajor la{(const uint16_t *)a, lda, K, M};
-  TnRowMajor lb{(const uint16_t *)b, ldb, K, N};
-  return launch_mix_gemm(TnStage<TnRowMajor>{la}, TnStage<TnRowMajor>{lb}, c,
-                         M, N, K, ldc, c_f32 != 0, s);
+  return launch_tn_tn_gemm(tn_tn_pipe_ok(M, N, lda, ldb), a, b, c, M, N, K,
+                           lda, ldb, LinearWriter{ldc}, ldc, c_f32 != 0, s);
 }
 
 // split-K form of gemm_tn_tn for weight-gradient shapes whose tile grid
 // underfills the chip (BERT attn-out dw = 64 workgroups on 256 CUs with a
 // K of batch*seq): fp32 slabs in `partial` [splits][M*ldc] reduced into a
 // dense fp32 C. Caller sizes `partial` with `splits` from gemm_tn_tn_splits.
-static bool linear_sk_on() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_LINEAR_SK");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
 extern "C" int gemm_tn_tn_splits(int M, int N, int K) {
   const bool off = !linear_sk_on();
   long tiles = ((M + 127) / 128) * ((N + 127) / 128);
@@ -329,27 +231,13 @@ extern "C" hipError_t gemm_tn_tn_sk(const void *a, const void *b,
   // out_bf16: write C in bf16 directly (weight-grad path — the fp32 C +
   // torch .to(bf16) cast afterwards was ~200 cast kernels / 1.3 ms per
   // BERT-Large step, prof8)
-  if (use_pipemix() && tn_cols_ok(M, lda) && tn_cols_ok(N, ldb)) {
-    TnPipe<PlainTnSrc> sa{{(const uint16_t *)a, lda, K, M}};
-    TnPipe<PlainTnSrc> sb{{(const uint16_t *)b, ldb, K, N}};
-    if (splits <= 1)
-      return launch_pipe_mix_wr(sa, sb, c, M, N, K, LinearWriter{ldc}, ldc,
-                                out_bf16 == 0, s);
-    hipError_t e = launch_pipe_mix_wr(sa, sb, partial, M, N, K,
-                                      LinearWriter{ldc}, ldc, true, s, splits);
-    if (e != hipSuccess) return e;
-    return splitk_reduce(partial, splits, (long)M * ldc, c, out_bf16, s);
-  }
-  TnRowMajor la{(const uint16_t *)a, lda, K, M};
-  TnRowMajor lb{(const uint16_t *)b, ldb, K, N};
-  if (splits <= 1)
-    return launch_mix_gemm(TnStage<TnRowMajor>{la}, TnStage<TnRowMajor>{lb},
-                           c, M, N, K, ldc, out_bf16 == 0, s);
-  hipError_t e = launch_mix_gemm(TnStage<TnRowMajor>{la},
-                                 TnStage<TnRowMajor>{lb}, partial, M, N, K,
-                                 ldc, true, s, splits);
-  if (e != hipSuccess) return e;
-  return splitk_reduce(partial, splits, (long)M * ldc, c, out_bf16, s);
+  const bool pipe_ok = tn_tn_pipe_ok(M, N, lda, ldb);
+  return launch_splitk(
+      [&](void *out, bool f32, int sp) {
+        return launch_tn_tn_gemm(pipe_ok, a, b, out, M, N, K, lda, ldb,
+                                 LinearWriter{ldc}, ldc, f32, s, sp);
+      },
+      partial, c, (long)M * ldc, splits, out_bf16, s);
 }
 
 // bf16 2-D transpose: out[j][i] = in[i][j], output leading dim ldo >= R
@@ -414,28 +302,6 @@ extern "C" hipError_t mfma_probe(const void *a, const void *b, float *d,
                                  hipStream_t s) {
   mfma_probe_k<<<1, 64, 0, s>>>((const uint16_t *)a, (const uint16_t *)b, d);
   return hipGetLastError();
-}
-
-// ---- route introspection (host only; tests/test_knob_routes.py) ----------
-// Each value is what this TU's launchers resolve — the same helpers, the
-// same per-process statics — so a test can prove a knob selected the route
-// it names. Order is the contract with bindings.cpp route_info().
-extern "C" void gemm_route_knobs(int *out) {
-  out[0] = use_pipemix();
-  out[1] = use_pipe8();
-  out[2] = use_p256x16();
-  out[3] = use_gemm256();
-  out[4] = use_pipe();
-  out[5] = use_pipent();
-  out[6] = use_glds();
-  out[7] = use_onebuf();
-  out[8] = use_splitmajor();
-  out[9] = use_sk_cpx();
-  out[10] = fwd_sk_on();
-  out[11] = dx_sk_mode();
-  out[12] = linear_sk_on();
-  out[13] = gelu_deriv_mode();
-  out[14] = gelubwd_wt_on();
 }
 
 // Process-wide switch of the 16-byte-store epilogue (mix_gemm.h): returns

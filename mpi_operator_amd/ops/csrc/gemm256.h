@@ -146,20 +146,12 @@ static hipError_t launch_nt256(const LA &la, const LB &lb, void *c, int M,
   int cpx = (nwg % 8 == 0 && nwg >= 32) ? nwg / 8 : 0;
   // compile-time bias split: a runtime `bias ? bias[col] : 0` select in
   // the epilogue measured 20.3 -> 37.6 us mean on the ResNet 1x1 shapes
-  if (c_f32) {
-    if (bias)
-      nt256_gemm_k<true, true><<<nwg, 512, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-    else
-      nt256_gemm_k<true, false><<<nwg, 512, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-  } else {
-    if (bias)
-      nt256_gemm_k<false, true><<<nwg, 512, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-    else
-      nt256_gemm_k<false, false><<<nwg, 512, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-  }
+  with_bool(c_f32, [&](auto f32) {
+    with_bool(bias != nullptr, [&](auto has_bias) {
+      nt256_gemm_k<decltype(f32)::value, decltype(has_bias)::value>
+          <<<nwg, 512, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
+                               tiles_n, cpx, bias);
+    });
+  });
   return hipGetLastError();
 }

@@ -7,6 +7,8 @@
 // Backward's dgamma/dbeta use per-block fp32 partial slabs reduced by the
 // existing splitk_reduce kernel (atomics on N addresses would serialize).
 #include "common.h"
+#include "knobs.h"
+#include "launchers.h"
 
 // y = (x - mean) * rstd * gamma + beta;  saves mean/rstd per row.
 // C8T: compile-time C8 specialization (0 = runtime). The runtime-bounded
@@ -331,36 +333,8 @@ __global__ void ln_gb_reduce_k(const float *__restrict__ partial,
     out[c] = red[0] + red[1] + red[2] + red[3];
 }
 
-// LN C8 specialization: same-box A/B at BERT-Large bs32 showed the
-// compile-time octet loops LOSE 2.4% (1384 vs 1415; ln_bwd_dx 15.5->24.1
-// us) — the unrolled form costs more than the runtime loop at M=4096
-// despite lower VGPRs. Default OFF; MPIAMD_LN_SPEC=1 enables for
-// small-shape A/Bs.
-static bool ln_spec() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_LN_SPEC");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
-// MPIAMD_LN2=1: 2-row-interleaved dx kernel (ln_bwd_dx2_k) for N <= 1024
-// (A/B lever). Default OFF.
-static bool ln2_mode() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_LN2");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
-// route introspection (host only): [ln_spec, ln2] as the launchers below
-// resolve them
-extern "C" void ln_route_knobs(int *out) {
-  out[0] = ln_spec();
-  out[1] = ln2_mode();
-}
-
+// The launchers below choose kernels by knobs.h ln_spec() (compile-time
+// octet loops at N = 1024 / 768) and ln2_mode() (2-row-interleaved dx).
 static int ln_grid(long M, int waves) {
   long g = (M + waves - 1) / waves;
   if (g > 1024) g = 1024;
@@ -410,9 +384,6 @@ extern "C" hipError_t ln_fwd_add(const void *a, const void *b,
   HIP_KERNEL_CHECK();
   return hipSuccess;
 }
-
-extern "C" hipError_t splitk_reduce(const float *, int, long, void *, int,
-                                    hipStream_t);
 
 // partial must hold [grid][2][N] fp32 (grid from *grid_out contract:
 // caller passes the allocation's row count); dgamma/dbeta are fp32 [N]

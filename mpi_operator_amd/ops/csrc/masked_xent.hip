@@ -12,6 +12,7 @@
 // fwd:  loss_sum += logsumexp(row) - x[target];  count += 1   (valid rows)
 // bwd:  dlogits = (exp(x - mx)·inv_sum - onehot) · dloss / count
 #include "common.h"
+#include "launchers.h"
 
 __global__ void masked_xent_fwd_k(const uint16_t *__restrict__ logits,
                                   const long *__restrict__ target,

@@ -24,7 +24,10 @@
 #pragma once
 #include <atomic>
 #include <cstdint>
+#include <type_traits>
 
+#include "knobs.h"
+#include "launchers.h"
 #include "mfma_tile.h"
 
 constexpr int MXP = 9; // slots per LDS image row (pitch 144 B)
@@ -730,26 +733,43 @@ __global__ __launch_bounds__(NT_THREADS) void mix_gemm_k(
 #undef MXG_A
 #undef MXG_B
 
-// MPIAMD_SPLITMAJOR=1: split-major dispatch of the mix split-K grid.
-// default OFF: the standalone-harness win (+16-28% on synthetic TnTn
-// wgrad shapes) did not transfer to the full model (-0.4% same-box on the
-// bench) — real wgrads gather B via XcolStage and use smaller splits
-static inline bool use_splitmajor() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_SPLITMAJOR");
-    return e && e[0] == '1';
-  }();
-  return on;
+// ---- launch geometry shared by every split-K tile launcher ----------------
+
+// Split count a launch really runs: at most one split per `bk`-deep k-tile.
+// A caller that reduces the slabs afterwards clamps with the same function,
+// so it sums exactly the slabs the GEMM wrote.
+static inline int clamp_splits(int splits, long K, int bk) {
+  long nk = (K + bk - 1) / bk;
+  return splits > nk ? (nk > 0 ? (int)nk : 1) : splits;
 }
 
-// MPIAMD_GEMM_ONEBUF=1: single-LDS-buffer mix tile (register-staged
-// operands only, see launch_mix_gemm_wr). Default OFF.
-static inline bool use_onebuf() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_GEMM_ONEBUF");
-    return e && e[0] == '1';
-  }();
-  return on;
+// Grid of a `tile`²-tile, `bk`-deep GEMM run in `splits` split-K slices
+// (mix_gemm_k, pipe_mix_k, pipe_mix8_k).
+struct TileGeom {
+  int tiles_n, splits, kts, nwg;
+  long split_stride; // elements between the fp32 slabs of two splits
+  TileGeom(int M, int N, int K, long ldc, int splits_in, int tile, int bk)
+      : tiles_n((N + tile - 1) / tile), splits(clamp_splits(splits_in, K, bk)),
+        kts(((K + bk - 1) / bk + splits - 1) / splits),
+        nwg(((M + tile - 1) / tile) * tiles_n), split_stride((long)M * ldc) {}
+  // T1 XCD swizzle: give each XCD a contiguous chunk of tiles so neighbor
+  // tiles (sharing operand panels) hit the same per-XCD L2. Needs nwg%8==0
+  // and enough tiles to matter; under split-K only where the launcher says
+  // so (`fold_sk`).
+  int cpx(bool fold_sk) const {
+    return (nwg % 8 == 0 && nwg >= 32 && (splits == 1 || fold_sk)) ? nwg / 8
+                                                                    : 0;
+  }
+};
+
+// f(std::true_type{}) or f(std::false_type{}): turns a runtime flag into a
+// kernel template argument with ONE launch statement in f instead of one
+// per value.
+template <class F> static inline void with_bool(bool b, F &&f) {
+  if (b)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
 }
 
 template <class SA, class SB, class WR>
@@ -757,36 +777,20 @@ static hipError_t launch_mix_gemm_wr(const SA &sa, const SB &sb, void *c,
                                      int M, int N, int K, const WR &wrt,
                                      long ldc, bool c_f32, hipStream_t s,
                                      int splits = 1) {
-  int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  int nk = (K + BK - 1) / BK;
-  if (splits > nk) splits = nk > 0 ? nk : 1;
-  int kts = (nk + splits - 1) / splits;
-  long split_stride = (long)M * ldc;
-  int nwg = tiles_m * tiles_n;
-  // T1 XCD swizzle: give each XCD a contiguous chunk of tiles so neighbor
-  // tiles (sharing operand panels) hit the same per-XCD L2. Needs nwg%8==0
-  // and enough tiles to matter.
-  int swap = (splits > 1 && splits % 8 == 0 && use_splitmajor()) ? 1 : 0;
-  int cpx = (nwg % 8 == 0 && nwg >= 32 && (splits == 1 || swap)) ? nwg / 8 : 0;
-  dim3 grid = swap ? dim3(splits, nwg) : dim3(nwg, splits);
+  const TileGeom g(M, N, K, ldc, splits, BM, BK);
+  int swap = (g.splits > 1 && g.splits % 8 == 0 && use_splitmajor()) ? 1 : 0;
+  int cpx = g.cpx(swap);
+  dim3 grid = swap ? dim3(g.splits, g.nwg) : dim3(g.nwg, g.splits);
   // glds targets the next buffer while the current one is being read — a
   // single buffer would race
   const bool onebuf = use_onebuf() && !SA::GLDS && !SB::GLDS;
-  if (onebuf) {
-    if (c_f32)
-      mix_gemm_k<SA, SB, true, WR, true><<<grid, NT_THREADS, 0, s>>>(
-          sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, swap);
-    else
-      mix_gemm_k<SA, SB, false, WR, true><<<grid, NT_THREADS, 0, s>>>(
-          sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, swap);
-    return hipGetLastError();
-  }
-  if (c_f32)
-    mix_gemm_k<SA, SB, true, WR><<<grid, NT_THREADS, 0, s>>>(
-        sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, swap);
-  else
-    mix_gemm_k<SA, SB, false, WR><<<grid, NT_THREADS, 0, s>>>(
-        sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, swap);
+  with_bool(c_f32, [&](auto f32) {
+    with_bool(onebuf, [&](auto ob) {
+      mix_gemm_k<SA, SB, decltype(f32)::value, WR, decltype(ob)::value>
+          <<<grid, NT_THREADS, 0, s>>>(sa, sb, c, M, N, K, wrt, g.tiles_n,
+                                       g.kts, g.split_stride, cpx, swap);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -810,44 +814,6 @@ static hipError_t launch_mix_gemm(const SA &sa, const SB &sb, void *c, int M,
 // forward (conv.hip conv_fwd_bn) runs exactly the kernel the unfused conv
 // runs for the same shape and environment.
 enum NtRoute { NT_PIPE256, NT_256, NT_PIPEMIX, NT_GLDS, NT_REG };
-
-// MPIAMD_GEMM256=0: no 256²-tile family (128² everywhere).
-static inline bool use_gemm256() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_GEMM256");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// 4-phase deep pipeline (pipe256.h) for K%64 full-tile shapes;
-// MPIAMD_PIPE=0 reverts to the round-1 BK=32 3-buffer kernel (gemm256.h)
-static inline bool use_pipe() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_PIPE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// MPIAMD_PIPENT=0 reverts just the NT 128² pipe fallback (bisect lever).
-static inline bool use_pipent() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_PIPENT");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// MPIAMD_GLDS=0: register-staged loads instead of global_load_lds in the
-// mix tile.
-static inline bool use_glds() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_GLDS");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
 
 static inline NtRoute nt_gemm_route(int M, int N, int K, long ldc, int kdim_a,
                                     int kdim_b, int splits) {
@@ -920,3 +886,56 @@ struct TnRowMajor {
     return v;
   }
 };
+
+// ---- k-strided (TN) operand routes ----
+// One rule for every GEMM with a plain TN operand: the deep pipeline
+// (pipe_mix.h) when `pipe_ok`, else the register-staged mix tile. The pipe
+// stages TN operands in 16-B column granules, so each caller passes its own
+// predicate — use_pipemix() and whatever makes its operands readable that
+// way (gemm.hip tn_cols_ok).
+
+// C[M][N] (+)= A[M][K-contiguous] · B(k-strided [K rows][N cols])
+template <class WR>
+static hipError_t launch_nt_tn_gemm(bool pipe_ok, const void *a, const void *b,
+                                    void *c, int M, int N, int K, long lda,
+                                    long ldb, const WR &wrt, long ldc,
+                                    bool c_f32, hipStream_t s, int splits = 1) {
+  if (pipe_ok) {
+    NtPipe<PlainNtSrc> sa{{(const uint16_t *)a, lda, M, K}};
+    TnPipe<PlainTnSrc> sb{{(const uint16_t *)b, ldb, K, N}};
+    return launch_pipe_mix_wr(sa, sb, c, M, N, K, wrt, ldc, c_f32, s, splits);
+  }
+  GemmLoader la{(const uint16_t *)a, M, lda, K};
+  TnRowMajor lb{(const uint16_t *)b, ldb, K, N};
+  return launch_mix_gemm_wr(NtStage<GemmLoader>{la}, TnStage<TnRowMajor>{lb},
+                            c, M, N, K, wrt, ldc, c_f32, s, splits);
+}
+
+// C[M][N] = Σ_k A(k-strided [K rows][M cols]) · B(k-strided [K rows][N cols])
+template <class WR>
+static hipError_t launch_tn_tn_gemm(bool pipe_ok, const void *a, const void *b,
+                                    void *c, int M, int N, int K, long lda,
+                                    long ldb, const WR &wrt, long ldc,
+                                    bool c_f32, hipStream_t s, int splits = 1) {
+  if (pipe_ok) {
+    TnPipe<PlainTnSrc> sa{{(const uint16_t *)a, lda, K, M}};
+    TnPipe<PlainTnSrc> sb{{(const uint16_t *)b, ldb, K, N}};
+    return launch_pipe_mix_wr(sa, sb, c, M, N, K, wrt, ldc, c_f32, s, splits);
+  }
+  TnRowMajor la{(const uint16_t *)a, lda, K, M};
+  TnRowMajor lb{(const uint16_t *)b, ldb, K, N};
+  return launch_mix_gemm_wr(TnStage<TnRowMajor>{la}, TnStage<TnRowMajor>{lb},
+                            c, M, N, K, wrt, ldc, c_f32, s, splits);
+}
+
+// Split-K tail: gemm(out, c_f32, splits) launches the GEMM. splits <= 1
+// writes C directly (fp32 iff !out_bf16); otherwise the GEMM fills the fp32
+// slabs in `partial` ([splits][len]) and splitk_reduce sums them into C.
+template <class GEMM>
+static hipError_t launch_splitk(GEMM gemm, float *partial, void *c, long len,
+                                int splits, int out_bf16, hipStream_t s) {
+  if (splits <= 1) return gemm(c, out_bf16 == 0, 1);
+  hipError_t e = gemm((void *)partial, true, splits);
+  if (e != hipSuccess) return e;
+  return splitk_reduce(partial, splits, len, c, out_bf16, s);
+}

@@ -19,6 +19,7 @@
 // partials slab with one slot per block, summed in index order: no atomics,
 // bit-reproducible run to run.
 #include "common.h"
+#include "launchers.h"
 
 constexpr int OPT_MAX_T = 40;
 constexpr int OPT_BLOCK = 256;
@@ -26,15 +27,6 @@ constexpr int OPT_EPB = OPT_BLOCK * 32; // elements per block (8192)
 constexpr int OPT_ROUND = OPT_BLOCK * 8; // elements per block per round
 
 enum { OPT_STEP = 0, OPT_LR = 1, OPT_BC1 = 2, OPT_BC2 = 3, OPT_CLIP = 4 };
-
-struct OptDesc {
-  const void *grad;
-  float *master;
-  float *m;
-  float *v;
-  uint16_t *out; // nullptr if the param itself is fp32 (master IS the param)
-  long numel;
-};
 
 struct OptArgs {
   OptDesc d[OPT_MAX_T];

@@ -380,16 +380,6 @@ __global__ __launch_bounds__(1024) void pipe256x16_gemm_k(
 }
 #undef P256X_IMG
 
-// Default ON: +0.4% same-box on BOTH models (BERT 1513->1520 seq/s,
-// ResNet101 3812->3829 img/s). MPIAMD_P256X16=0 reverts to 8 waves.
-static inline bool use_p256x16() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_P256X16");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // Writer-parameterized launch (fused epilogues: GELU+bias, BN stats, ...)
 template <class WR, class LA, class LB>
 static hipError_t launch_pipe256_wr(const LA &la, const LB &lb, void *c,
@@ -399,36 +389,29 @@ static hipError_t launch_pipe256_wr(const LA &la, const LB &lb, void *c,
   int nwg = tiles_m * tiles_n;
   int cpx = (nwg % 8 == 0 && nwg >= 32) ? nwg / 8 : 0;
   constexpr int SWZ = 1, NPB = 1, SP = 1;
+  auto launch16 = [&](auto f32, auto vec) {
+    pipe256x16_gemm_k<decltype(f32)::value, false, SWZ, SP, WR, true,
+                      decltype(vec)::value>
+        <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
+                              tiles_n, cpx, nullptr, wrt);
+  };
   if (use_p256x16()) {
+    // the VEC kernels exist only for writers with a row-major epilogue
+    bool vec = false;
     if constexpr (WR::VEC) {
-      if (epilogue_vec_eligible(wrt, c, N, c_f32, 1, 0)) {
-        if (c_f32)
-          pipe256x16_gemm_k<true, false, SWZ, SP, WR, true, true>
-              <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
-                                    tiles_n, cpx, nullptr, wrt);
-        else
-          pipe256x16_gemm_k<false, false, SWZ, SP, WR, true, true>
-              <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
-                                    tiles_n, cpx, nullptr, wrt);
-        return hipGetLastError();
-      }
+      vec = epilogue_vec_eligible(wrt, c, N, c_f32, 1, 0);
+      if (vec)
+        with_bool(c_f32, [&](auto f32) { launch16(f32, std::true_type{}); });
     }
-    if (c_f32)
-      pipe256x16_gemm_k<true, false, SWZ, SP, WR, true><<<nwg, 1024, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, nullptr,
-          wrt);
-    else
-      pipe256x16_gemm_k<false, false, SWZ, SP, WR, true><<<nwg, 1024, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, nullptr,
-          wrt);
+    if (!vec)
+      with_bool(c_f32, [&](auto f32) { launch16(f32, std::false_type{}); });
     return hipGetLastError();
   }
-  if (c_f32)
-    pipe256_gemm_k<true, false, SWZ, NPB, SP, WR, true><<<nwg, 512, 0, s>>>(
-        la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, nullptr, wrt);
-  else
-    pipe256_gemm_k<false, false, SWZ, NPB, SP, WR, true><<<nwg, 512, 0, s>>>(
-        la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, nullptr, wrt);
+  with_bool(c_f32, [&](auto f32) {
+    pipe256_gemm_k<decltype(f32)::value, false, SWZ, NPB, SP, WR, true>
+        <<<nwg, 512, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
+                             tiles_n, cpx, nullptr, wrt);
+  });
   return hipGetLastError();
 }
 
@@ -443,50 +426,24 @@ static hipError_t launch_pipe256(const LA &la, const LB &lb, void *c, int M,
   // swz1 + 1 barrier/phase + static setprio: 1146 TF @4k³ vs 789 for the
   // round-1 gemm256 (+44%); +17-42% on the real model shapes
   constexpr int SWZ = 1, NPB = 1, SP = 1;
-  if (use_p256x16()) {
-    if (!bias &&
+  with_bool(c_f32, [&](auto f32) {
+    constexpr bool F32 = decltype(f32)::value;
+    if (use_p256x16() && !bias &&
         epilogue_vec_eligible(LinearWriter{ldc}, c, N, c_f32, 1, 0)) {
-      if (c_f32)
-        pipe256x16_gemm_k<true, false, SWZ, SP, LinearWriter, false, true>
-            <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
-                                  tiles_n, cpx, bias);
-      else
-        pipe256x16_gemm_k<false, false, SWZ, SP, LinearWriter, false, true>
-            <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
-                                  tiles_n, cpx, bias);
-      return hipGetLastError();
+      pipe256x16_gemm_k<F32, false, SWZ, SP, LinearWriter, false, true>
+          <<<nwg, 1024, 0, s>>>(la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc,
+                                tiles_n, cpx, bias);
+      return;
     }
-    if (c_f32) {
-      if (bias)
-        pipe256x16_gemm_k<true, true, SWZ, SP><<<nwg, 1024, 0, s>>>(
+    with_bool(bias != nullptr, [&](auto has_bias) {
+      constexpr bool BIAS = decltype(has_bias)::value;
+      if (use_p256x16())
+        pipe256x16_gemm_k<F32, BIAS, SWZ, SP><<<nwg, 1024, 0, s>>>(
             la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
       else
-        pipe256x16_gemm_k<true, false, SWZ, SP><<<nwg, 1024, 0, s>>>(
+        pipe256_gemm_k<F32, BIAS, SWZ, NPB, SP><<<nwg, 512, 0, s>>>(
             la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-    } else {
-      if (bias)
-        pipe256x16_gemm_k<false, true, SWZ, SP><<<nwg, 1024, 0, s>>>(
-            la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-      else
-        pipe256x16_gemm_k<false, false, SWZ, SP><<<nwg, 1024, 0, s>>>(
-            la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-    }
-    return hipGetLastError();
-  }
-  if (c_f32) {
-    if (bias)
-      pipe256_gemm_k<true, true, SWZ, NPB, SP><<<nwg, 512, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-    else
-      pipe256_gemm_k<true, false, SWZ, NPB, SP><<<nwg, 512, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-  } else {
-    if (bias)
-      pipe256_gemm_k<false, true, SWZ, NPB, SP><<<nwg, 512, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-    else
-      pipe256_gemm_k<false, false, SWZ, NPB, SP><<<nwg, 512, 0, s>>>(
-          la.p, la.ld, lb.p, lb.ld, c, M, N, K, ldc, tiles_n, cpx, bias);
-  }
+    });
+  });
   return hipGetLastError();
 }

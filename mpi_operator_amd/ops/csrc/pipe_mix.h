@@ -52,70 +52,6 @@
 
 typedef __attribute__((ext_vector_type(2))) unsigned int uint2v_pm;
 
-// MPIAMD_PIPEMIX=0 reverts every pipe_mix route to the round-1 register-
-// staged mix_gemm tile (A/B lever).
-static inline bool use_pipemix() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_PIPEMIX");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// The conv GATHER routes measured net-negative on the 4-WAVE pipeline
-// (3296 vs 3390 same-box), but the verdict REVERSED under the 8-wave
-// kernel: 3742 -> 3820 img/s ResNet101 / 6508 ResNet50 same-box — the
-// extra VALU of the gather ptr16 hides behind the doubled wave count.
-// Default ON; MPIAMD_PIPEGATHER=0 reverts to the register-staged mix
-// gathers.
-static inline bool use_pipegather() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_PIPEGATHER");
-    return !(e && e[0] == '0');
-  }();
-  return use_pipemix() && on;
-}
-
-// wgrad-only override: the -2.9% PIPEGATHER measurement bundled fwd/dgrad
-// and wgrad gathers; A/B'd alone the Xcol wgrad pipe WINS (3566 -> 3573
-// img/s ResNet101, 6129 ResNet50 same-box) — default ON.
-// The three gates nest: MPIAMD_PIPEMIX=0 reverts everything,
-// MPIAMD_PIPEGATHER=0 reverts the fwd, dgrad AND wgrad gathers, and
-// MPIAMD_PIPEGATHER_WGRAD=0 reverts the wgrad gather alone to the
-// register-staged mix gather. (Until PIPEGATHER defaulted on this was
-// `(pipemix && wgrad) || pipegather`, which made WGRAD=0 a no-op and left
-// wgrad on the pipe under PIPEGATHER=0.)
-static inline bool use_pipegather_wgrad() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_PIPEGATHER_WGRAD");
-    return !(e && e[0] == '0');
-  }();
-  return use_pipegather() && on;
-}
-
-// Stride-2 dgrad parity GEMMs on the pipe (conv.hip conv_dgrad_s2);
-// MPIAMD_PIPES2=0 keeps them on DgradS2Stage while every other gather
-// stays on the pipe (A/B lever).
-static inline bool use_pipes2() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_PIPES2");
-    return !(e && e[0] == '0');
-  }();
-  return use_pipegather() && on;
-}
-
-// XCD fold also applies under split-K: the 2-D grid dispatches x-fastest,
-// so within each split slice consecutive tile ids still round-robin the
-// XCDs and the fold restores contiguous tile bands per XCD L2.
-// MPIAMD_SK_CPX=0 restores the old splits==1-only gate for A/B.
-static inline bool use_sk_cpx() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_SK_CPX");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // ---- SrcMaps ----------------------------------------------------------
 // concept (stateful: each thread stages the same 2 (row/col, k-offset)
 // granules every k-tile, so the expensive decomposition hoists into init):
@@ -657,7 +593,6 @@ template <class SRC> struct Tn8Pipe;
 template <class P> struct Pipe8Of;
 template <class S> struct Pipe8Of<NtPipe<S>> { using type = Nt8Pipe<S>; };
 template <class S> struct Pipe8Of<TnPipe<S>> { using type = Tn8Pipe<S>; };
-static inline bool use_pipe8();
 template <class SA8, class SB8, class WR>
 static hipError_t launch_pipe_mix8_wr(const SA8 &sa, const SB8 &sb, void *c,
                                       int M, int N, int K, const WR &wrt,
@@ -677,21 +612,13 @@ static hipError_t launch_pipe_mix_wr(const SA &sa, const SB &sb, void *c,
                                wrt, ldc, c_f32, s, splits);
   const uint16_t *zeros = pm_zeros_page();
   if (!zeros) return hipErrorOutOfMemory;
-  int tiles_m = (M + PM_BM - 1) / PM_BM, tiles_n = (N + PM_BM - 1) / PM_BM;
-  int nk = (K + PM_BK - 1) / PM_BK;
-  if (splits > nk) splits = nk > 0 ? nk : 1;
-  int kts = (nk + splits - 1) / splits;
-  long split_stride = (long)M * ldc;
-  int nwg = tiles_m * tiles_n;
-  int cpx = (nwg % 8 == 0 && nwg >= 32 && (splits == 1 || use_sk_cpx()))
-                ? nwg / 8 : 0;
-  dim3 grid(nwg, splits);
-  if (c_f32)
-    pipe_mix_k<SA, SB, true, WR><<<grid, PM_THREADS, 0, s>>>(
-        sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, 0, zeros);
-  else
-    pipe_mix_k<SA, SB, false, WR><<<grid, PM_THREADS, 0, s>>>(
-        sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, 0, zeros);
+  const TileGeom g(M, N, K, ldc, splits, PM_BM, PM_BK);
+  dim3 grid(g.nwg, g.splits);
+  with_bool(c_f32, [&](auto f32) {
+    pipe_mix_k<SA, SB, decltype(f32)::value, WR><<<grid, PM_THREADS, 0, s>>>(
+        sa, sb, c, M, N, K, wrt, g.tiles_n, g.kts, g.split_stride,
+        g.cpx(use_sk_cpx()), 0, zeros);
+  });
   return hipGetLastError();
 }
 
@@ -892,19 +819,6 @@ __global__ __launch_bounds__(512) void pipe_mix8_k(
 }
 #undef PM8_IMG
 
-// Default ON: same-box A/B with the 8-wave kernel on every pipe route —
-// BERT-Large bs32 1421 -> 1468 seq/s, bs8 607 -> 684, ResNet101
-// 3560 -> 3697 img/s. The extra waves (16/CU vs 8 at the same 64 KiB LDS
-// footprint) buy more than the duplicated B-frag LDS reads cost.
-// MPIAMD_PIPE8=0 reverts to the 4-wave kernel.
-static inline bool use_pipe8() {
-  static const bool on = [] {
-    const char *e = getenv("MPIAMD_PIPE8");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 template <class SA8, class SB8, class WR>
 static hipError_t launch_pipe_mix8_wr(const SA8 &sa, const SB8 &sb, void *c,
                                       int M, int N, int K, const WR &wrt,
@@ -912,33 +826,20 @@ static hipError_t launch_pipe_mix8_wr(const SA8 &sa, const SB8 &sb, void *c,
                                       int splits) {
   const uint16_t *zeros = pm_zeros_page();
   if (!zeros) return hipErrorOutOfMemory;
-  int tiles_m = (M + PM_BM - 1) / PM_BM, tiles_n = (N + PM_BM - 1) / PM_BM;
-  int nk = (K + PM_BK - 1) / PM_BK;
-  if (splits > nk) splits = nk > 0 ? nk : 1;
-  int kts = (nk + splits - 1) / splits;
-  long split_stride = (long)M * ldc;
-  int nwg = tiles_m * tiles_n;
-  // same MPIAMD_SK_CPX gate as the 4-wave launcher (the 8-wave copy had
-  // dropped it, so the knob did nothing under the default MPIAMD_PIPE8)
-  int cpx = (nwg % 8 == 0 && nwg >= 32 && (splits == 1 || use_sk_cpx()))
-                ? nwg / 8 : 0;
-  dim3 grid(nwg, splits);
+  // the same geometry and MPIAMD_SK_CPX gate as the 4-wave launcher
+  const TileGeom g(M, N, K, ldc, splits, PM_BM, PM_BK);
+  dim3 grid(g.nwg, g.splits);
+  auto launch = [&](auto f32, auto vec) {
+    pipe_mix8_k<SA8, SB8, decltype(f32)::value, WR, decltype(vec)::value>
+        <<<grid, 512, 0, s>>>(sa, sb, c, M, N, K, wrt, g.tiles_n, g.kts,
+                              g.split_stride, g.cpx(use_sk_cpx()), 0, zeros);
+  };
+  // the VEC kernels exist only for writers that have a row-major epilogue
+  bool vec = false;
   if constexpr (WR::VEC) {
-    if (epilogue_vec_eligible(wrt, c, N, c_f32, splits, split_stride)) {
-      if (c_f32)
-        pipe_mix8_k<SA8, SB8, true, WR, true><<<grid, 512, 0, s>>>(
-            sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, 0, zeros);
-      else
-        pipe_mix8_k<SA8, SB8, false, WR, true><<<grid, 512, 0, s>>>(
-            sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, 0, zeros);
-      return hipGetLastError();
-    }
+    vec = epilogue_vec_eligible(wrt, c, N, c_f32, g.splits, g.split_stride);
+    if (vec) with_bool(c_f32, [&](auto f32) { launch(f32, std::true_type{}); });
   }
-  if (c_f32)
-    pipe_mix8_k<SA8, SB8, true, WR><<<grid, 512, 0, s>>>(
-        sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, 0, zeros);
-  else
-    pipe_mix8_k<SA8, SB8, false, WR><<<grid, 512, 0, s>>>(
-        sa, sb, c, M, N, K, wrt, tiles_n, kts, split_stride, cpx, 0, zeros);
+  if (!vec) with_bool(c_f32, [&](auto f32) { launch(f32, std::false_type{}); });
   return hipGetLastError();
 }

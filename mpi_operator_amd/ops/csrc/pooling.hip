@@ -1,6 +1,7 @@
 // Max-pool fwd (+argmax u8) and gather-style bwd for NHWC bf16.
 // Reference op: tf_cnn_benchmarks ResNet stem max-pool.
 #include "common.h"
+#include "launchers.h"
 
 // fwd: one lane-task per (output pixel, 8-channel group); 16 B loads.
 __global__ void maxpool_fwd_k(const ushort8 *__restrict__ x,

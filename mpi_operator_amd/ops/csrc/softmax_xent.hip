@@ -1,6 +1,7 @@
 // Fused softmax + cross-entropy (mean reduction) for the classifier head.
 // logits bf16 [B,V] → loss fp32 scalar + probs fp32 [B,V] (saved for bwd).
 #include "common.h"
+#include "launchers.h"
 
 __global__ void softmax_xent_fwd_k(const uint16_t *__restrict__ logits,
                                    const long *__restrict__ target,

@@ -3,9 +3,9 @@
 The knobs are read once per process into function-local statics, so each
 configuration runs in a fresh child that imports the extension and prints
 ``route_info()`` plus a few ``nt_route(...)`` results as JSON; the parent
-asserts the table below. ``route_info`` reports from the helpers the
-launchers themselves call (extern "C" from the .hip file that owns each
-knob), so a knob the dispatch ignores cannot pass. None of this touches the
+asserts the table below. Every knob is one inline function of
+``csrc/knobs.h`` and ``route_info()`` calls the very functions the launchers
+call, so a knob the dispatch ignores cannot pass. None of this touches the
 device: the extension imports on a CPU-only machine, so these tests are
 unmarked.
 
@@ -239,11 +239,17 @@ def test_this_process_matches_its_knobs():
 
 
 def test_knobs_documented():
-    """getenv names in csrc == route_info() keys, each in a docs table row."""
+    """Knob names read in knobs.h == route_info() keys, each in a docs table
+    row; no other csrc file reads the environment."""
     names = set()
     for path in glob.glob(os.path.join(CSRC, "*")):
         with open(path, encoding="utf-8") as f:
-            names |= set(re.findall(r'getenv\(\s*"(MPIAMD_[A-Z0-9_]+)"', f.read()))
+            text = f.read()
+        if os.path.basename(path) == "knobs.h":
+            names = set(re.findall(r'\bknob_\w+\(\s*"(MPIAMD_[A-Z0-9_]+)"',
+                                   text))
+        else:
+            assert "getenv(" not in text, path
     info = child_routes({})[0]
     assert set(info) == set(DEFAULT_INFO)
     assert names == {KNOB_ENV[k] for k in info}, \
