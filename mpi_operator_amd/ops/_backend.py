@@ -33,6 +33,13 @@ def _try_load():
         # "0" keeps the one-element-per-lane stores (A/B lever)
         if os.environ.get("MPIAMD_EPI_VEC", "1") == "0":
             _ext.set_epilogue_vec(False)
+        # MPIAMD_BN_PIPELINED (default "1"): software-pipelined BN statistics
+        # producers; MPIAMD_BN_FINALIZE_COALESCED (default "1"): line-coalesced
+        # BN finalize. "0" keeps the kernels they replace (A/B levers)
+        if os.environ.get("MPIAMD_BN_PIPELINED", "1") == "0":
+            _ext.set_bn_pipelined(False)
+        if os.environ.get("MPIAMD_BN_FINALIZE_COALESCED", "1") == "0":
+            _ext.set_bn_finalize_coalesced(False)
     except Exception as e:  # pragma: no cover - exercised on GPU boxes only
         _ext_err = e
 

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "knobs.h"
 #include "launchers.h"
+#include <atomic>
 
 // Per-thread fixed channel-group ownership: thread t owns channel block
 // cb = t % C8 and row-lane t / C8 — consecutive lanes read consecutive
@@ -640,6 +641,497 @@ __global__ void bn_bwd_apply_k(const ushort8 *__restrict__ dy,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Software-pipelined forms of the statistics producers above that gate dy by
+// a ReLU bitmask (MPIAMD_BN_PIPELINED): bn_partials_k<1> with a mask and
+// bn_join_stats_k<1, *>. Geometry, row assignment, the per-thread serial
+// chain a += f(row) + f(row + stride) and the block tail are the ones above;
+// only the memory schedule differs: the loads of the next BN_PIPE_DEPTH
+// pair-iterations are in flight while the current one is consumed. A grid of
+// at most 512 blocks puts two waves on a SIMD, so nothing else covers the HBM
+// latency between a thread's iterations. The other forms (forward statistics,
+// no ReLU, the y > 0 gate, JOIN 0, the split-K reduces, which never run more
+// than two pair-iterations) measured no faster pipelined and keep the kernels
+// above; profiles/BENCH_HISTORY.md has the figures.
+//
+// How a prefetch stays inside its tensor: every tensor is read (and dxt
+// written) through a buffer descriptor whose extent is exactly the tensor's
+// byte size, and a lane whose row is >= M is given the offset BN_OOB, which
+// is past every extent the launchers admit (< 2^31 bytes, bn_pipe_ok). The
+// hardware range check returns zero for such a lane without a memory access
+// (the zero `has2` substitutes above) and drops such a store. So the last
+// iterations need no special case: the loads for rows M .. M + depth·step
+// come back as zeros, their accumulation is discarded by the `ok` select,
+// and nothing outside [base, base + bytes) is ever addressed. An operand a
+// form does not have (xd, jmask) gets a zero-extent descriptor.
+//
+// Why descriptors rather than `row < M ? p[off] : 0`: a conditional load is a
+// branch, and after a branch that may skip a load the compiler has to wait
+// for all outstanding loads (it counts them statically), which undoes the
+// pipeline. With range-checked loads one group of BN_PIPE_DEPTH + 1
+// iterations has no branch around a load and the waits are counted. The
+// sched_barriers keep the compiler from sinking an iteration's prefetch below
+// the arithmetic of the iterations that follow it in the block (it did).
+#ifndef MPIAMD_BN_PIPE_DEPTH
+// 1 measured better than 2 (tools/bn_bench.py); 3 leaves the NSTAT 2 form one
+// wave per SIMD (256 VGPRs and AGPR spills), half of what its grid needs
+#define MPIAMD_BN_PIPE_DEPTH 1
+#endif
+constexpr int BN_PD = MPIAMD_BN_PIPE_DEPTH;
+constexpr unsigned BN_OOB = 0x80000000u;
+typedef __attribute__((ext_vector_type(4))) unsigned int uint4v;
+typedef __amdgpu_buffer_rsrc_t bn_rsrc_t;
+
+DEV_INLINE bn_rsrc_t bn_rsrc(const void *p, long bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)p, 0, (int)bytes,
+                                           0x00020000);
+}
+DEV_INLINE ushort8 bn_ld16(bn_rsrc_t r, unsigned byte_off) {
+  return __builtin_bit_cast(
+      ushort8, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
+}
+DEV_INLINE int bn_ld1(bn_rsrc_t r, unsigned byte_off) {
+  return (int)__builtin_amdgcn_raw_buffer_load_b8(r, byte_off, 0, 0);
+}
+DEV_INLINE void bn_st16(bn_rsrc_t r, unsigned byte_off, ushort8 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), r,
+                                         byte_off, 0, 0);
+}
+// index of the 16 B group (row, cb), or BN_OOB for a row past the end; the
+// mask's byte offset as it is, the activations' after bn_off16
+DEV_INLINE unsigned bn_off(long row, long M, int C8, int cb) {
+  return row < M ? (unsigned)(row * C8 + cb) : BN_OOB;
+}
+DEV_INLINE unsigned bn_off16(unsigned e) {
+  return e == BN_OOB ? BN_OOB : e * 16;
+}
+
+// bn_acc_bwd's accumulation step (fdy/fdy2 already gated); `ok` false leaves
+// the accumulators as they were
+DEV_INLINE void bn_acc_bwd_sel(float *a0, float *a1, const float *fx,
+                               const float *fx2, const float *fdy,
+                               const float *fdy2, const float *mn,
+                               const float *is, bool ok) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float n0 = __fadd_rn(a0[j], __fadd_rn(fdy[j], fdy2[j]));
+    float xh = __fmul_rn(__fsub_rn(fx[j], mn[j]), is[j]);
+    float xh2 = __fmul_rn(__fsub_rn(fx2[j], mn[j]), is[j]);
+    float n1 =
+        __fadd_rn(a1[j], __fmaf_rn(fdy[j], xh, __fmul_rn(fdy2[j], xh2)));
+    a0[j] = ok ? n0 : a0[j];
+    a1[j] = ok ? n1 : a1[j];
+  }
+}
+
+// ReLU gate of one row by its bitmask
+DEV_INLINE void bn_gate(float *fdy, int m) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) fdy[j] = (m & (1 << j)) ? fdy[j] : 0.f;
+}
+
+struct BnPartialsStage {
+  ushort8 x, x2, dy, dy2;
+  int m, m2;
+};
+
+// bn_partials_k<1> with relu and a bitmask
+__global__ void __launch_bounds__(256)
+bn_partials_bwd_pipe_k(const ushort8 *__restrict__ x,
+                       const ushort8 *__restrict__ dy,
+                       const uint8_t *__restrict__ mask,
+                       const float *__restrict__ mean,
+                       const float *__restrict__ invstd,
+                       float *__restrict__ partial, // [grid][2][C]
+                       long M, int C8) {
+  int cb = threadIdx.x % C8;
+  int row_lane = threadIdx.x / C8;
+  int rows_per_block = blockDim.x / C8;
+  float a0[8] = {0}, a1[8] = {0};
+  float mn[8], is[8];
+  if (row_lane < rows_per_block) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      mn[j] = mean[cb * 8 + j];
+      is[j] = invstd[cb * 8 + j];
+    }
+  }
+  if (row_lane < rows_per_block) {
+    const long stride = (long)gridDim.x * rows_per_block, step = 2 * stride;
+    const long nb = M * C8 * 16;
+    const bn_rsrc_t rx = bn_rsrc(x, nb), rdy = bn_rsrc(dy, nb);
+    const bn_rsrc_t rm = bn_rsrc(mask, M * C8);
+    auto load = [&](BnPartialsStage &b, long r) {
+      unsigned e = bn_off(r, M, C8, cb), e2 = bn_off(r + stride, M, C8, cb);
+      b.x = bn_ld16(rx, bn_off16(e));
+      b.x2 = bn_ld16(rx, bn_off16(e2));
+      b.dy = bn_ld16(rdy, bn_off16(e));
+      b.dy2 = bn_ld16(rdy, bn_off16(e2));
+      b.m = bn_ld1(rm, e);
+      b.m2 = bn_ld1(rm, e2);
+    };
+    BnPartialsStage buf[BN_PD + 1];
+    long row = (long)blockIdx.x * rows_per_block + row_lane;
+#pragma unroll
+    for (int k = 0; k < BN_PD; ++k) load(buf[k], row + k * step);
+    while (row < M) {
+#pragma unroll
+      for (int k = 0; k <= BN_PD; ++k) {
+        load(buf[(k + BN_PD) % (BN_PD + 1)], row + BN_PD * step);
+        __builtin_amdgcn_sched_barrier(0);
+        const BnPartialsStage &b = buf[k];
+        float fx[8], fx2[8], fdy[8], fdy2[8];
+        bf8_to_f8(b.x, fx);
+        bf8_to_f8(b.x2, fx2);
+        bf8_to_f8(b.dy, fdy);
+        bf8_to_f8(b.dy2, fdy2);
+        bn_gate(fdy, b.m);
+        bn_gate(fdy2, b.m2);
+        bn_acc_bwd_sel(a0, a1, fx, fx2, fdy, fdy2, mn, is, row < M);
+        row += step;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block);
+}
+
+struct BnJoinStage {
+  ushort8 a, a2, b, b2, x, x2, xd, xd2;
+  int jm, jm2, cm, cm2;
+};
+
+// bn_join_stats_k<1, NSTAT>
+template <int NSTAT>
+__global__ void __launch_bounds__(256)
+bn_join_stats_pipe_k(const ushort8 *__restrict__ a,
+                     const uint8_t *__restrict__ jmask,
+                     const ushort8 *__restrict__ b, ushort8 *__restrict__ dxt,
+                     const uint8_t *__restrict__ cmask,
+                     const ushort8 *__restrict__ x,
+                     const float *__restrict__ mean,
+                     const float *__restrict__ invstd,
+                     float *__restrict__ partial, // [grid][2][C]
+                     const ushort8 *__restrict__ xd,
+                     const float *__restrict__ mean_d,
+                     const float *__restrict__ invstd_d,
+                     float *__restrict__ partial_d, long M, int C8) {
+  int cb = threadIdx.x % C8;
+  int row_lane = threadIdx.x / C8;
+  int rows_per_block = blockDim.x / C8;
+  float a0[8] = {0}, a1[8] = {0}, d0[8] = {0}, d1[8] = {0};
+  float mn[8], is[8], mnd[8], isd[8];
+  if (row_lane < rows_per_block) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      mn[j] = mean[cb * 8 + j];
+      is[j] = invstd[cb * 8 + j];
+      if (NSTAT == 2) {
+        mnd[j] = mean_d[cb * 8 + j];
+        isd[j] = invstd_d[cb * 8 + j];
+      }
+    }
+  }
+  if (row_lane < rows_per_block) {
+    const long stride = (long)gridDim.x * rows_per_block, step = 2 * stride;
+    const long nb = M * C8 * 16;
+    const bn_rsrc_t ra = bn_rsrc(a, nb), rb = bn_rsrc(b, nb);
+    const bn_rsrc_t rx = bn_rsrc(x, nb), ro = bn_rsrc(dxt, nb);
+    const bn_rsrc_t rxd = bn_rsrc(xd, NSTAT == 2 ? nb : 0);
+    const bn_rsrc_t rjm = bn_rsrc(jmask, M * C8), rcm = bn_rsrc(cmask, M * C8);
+    auto load = [&](BnJoinStage &s, long r) {
+      unsigned e = bn_off(r, M, C8, cb), e2 = bn_off(r + stride, M, C8, cb);
+      unsigned o = bn_off16(e), o2 = bn_off16(e2);
+      s.a = bn_ld16(ra, o);
+      s.b = bn_ld16(rb, o);
+      s.x = bn_ld16(rx, o);
+      s.a2 = bn_ld16(ra, o2);
+      s.b2 = bn_ld16(rb, o2);
+      s.x2 = bn_ld16(rx, o2);
+      if (NSTAT == 2) {
+        s.xd = bn_ld16(rxd, o);
+        s.xd2 = bn_ld16(rxd, o2);
+      }
+      s.jm = bn_ld1(rjm, e);
+      s.jm2 = bn_ld1(rjm, e2);
+      s.cm = bn_ld1(rcm, e);
+      s.cm2 = bn_ld1(rcm, e2);
+    };
+    BnJoinStage buf[BN_PD + 1];
+    long row = (long)blockIdx.x * rows_per_block + row_lane;
+#pragma unroll
+    for (int k = 0; k < BN_PD; ++k) load(buf[k], row + k * step);
+    while (row < M) {
+#pragma unroll
+      for (int k = 0; k <= BN_PD; ++k) {
+        load(buf[(k + BN_PD) % (BN_PD + 1)], row + BN_PD * step);
+        __builtin_amdgcn_sched_barrier(0);
+        const BnJoinStage &s = buf[k];
+        ushort8 vo, vo2;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float g = (s.jm & (1 << j)) ? bf2f(s.a[j]) : 0.f;
+          float g2 = (s.jm2 & (1 << j)) ? bf2f(s.a2[j]) : 0.f;
+          vo[j] = f2bf(g + bf2f(s.b[j]));
+          vo2[j] = f2bf(g2 + bf2f(s.b2[j]));
+        }
+        // a row >= M has the offset BN_OOB: the store is dropped
+        bn_st16(ro, bn_off16(bn_off(row, M, C8, cb)), vo);
+        bn_st16(ro, bn_off16(bn_off(row + stride, M, C8, cb)), vo2);
+        float fo[8], fo2[8], fx[8], fx2[8];
+        bf8_to_f8(vo, fo);
+        bf8_to_f8(vo2, fo2);
+        bf8_to_f8(s.x, fx);
+        bf8_to_f8(s.x2, fx2);
+        bn_gate(fo, s.cm);
+        bn_gate(fo2, s.cm2);
+        bn_acc_bwd_sel(a0, a1, fx, fx2, fo, fo2, mn, is, row < M);
+        if (NSTAT == 2) {
+          float fxd[8], fxd2[8];
+          bf8_to_f8(s.xd, fxd);
+          bf8_to_f8(s.xd2, fxd2);
+          bn_acc_bwd_sel(d0, d1, fxd, fxd2, fo, fo2, mnd, isd, row < M);
+        }
+        row += step;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block);
+  if (NSTAT == 2) {
+    __syncthreads(); // one static LDS array, as in bn_join_stats_k
+    bn_block_store(d0, d1, partial_d, C8, cb, row_lane, rows_per_block);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Line-coalesced finalize (MPIAMD_BN_FINALIZE_COALESCED): a 256-thread block
+// owns CH consecutive channels (8 or 16), lane = channel within the slice, so
+// a load instruction reads CH·4 contiguous bytes of each slab row it touches
+// where the bands kernels read 4 B of 64 different lines. The summation tree
+// is the bands kernels', bit for bit:
+//   chains   s_t = Σ p[g], g ≡ t (mod 256) ascending, t = 0..255;
+//   butterfly over each 64 consecutive t, offsets 32, 16, 8, 4, 2, 1;
+//   ((r0 + r1) + r2) + r3.
+// Thread (ch, rg), rg = tid / CH, holds the CH chains t = rg + k·RG
+// (RG = 256/CH), i.e. wave w = k / (CH/4), lane-in-wave rg + RG·(k % (CH/4)):
+// the butterfly levels >= RG pair registers of one thread, the levels < RG
+// pair row groups and go through LDS. Addition commutes, so which partner
+// holds the result does not matter, only the tree.
+// The slab is read through a range-checked descriptor (see above): a (g, c)
+// outside [0, grid) x [0, C) reads nothing and is not accumulated.
+template <int CH>
+DEV_INLINE bool bn_fin_co_sums(const float *__restrict__ partial, int grid,
+                               int C, float &r0, float &r1) {
+  constexpr int RG = 256 / CH, KK = CH / 4;
+  const int ch = threadIdx.x % CH, rg = threadIdx.x / CH;
+  const int c = blockIdx.x * CH + ch;
+  const bn_rsrc_t rp = bn_rsrc(partial, (long)grid * 2 * C * 4);
+  float p0[CH], p1[CH];
+#pragma unroll
+  for (int k = 0; k < CH; ++k) p0[k] = p1[k] = 0.f;
+  for (int base = 0; base < grid; base += 256) {
+    float v0[CH], v1[CH];
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      int g = base + rg + k * RG;
+      bool ok = g < grid && c < C;
+      unsigned o = ok ? ((unsigned)g * 2 * C + c) * 4 : BN_OOB;
+      unsigned o1 = ok ? ((unsigned)g * 2 * C + C + c) * 4 : BN_OOB;
+      v0[k] = __builtin_bit_cast(
+          float, __builtin_amdgcn_raw_buffer_load_b32(rp, o, 0, 0));
+      v1[k] = __builtin_bit_cast(
+          float, __builtin_amdgcn_raw_buffer_load_b32(rp, o1, 0, 0));
+    }
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      bool ok = base + rg + k * RG < grid;
+      p0[k] = ok ? p0[k] + v0[k] : p0[k];
+      p1[k] = ok ? p1[k] + v1[k] : p1[k];
+    }
+  }
+  __shared__ float red[2 * 4 * 256]; // [stat][wave][rg][ch]
+  __shared__ float red2[2 * 4 * CH]; // [stat][wave][ch]
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+#pragma unroll
+    for (int off = KK / 2; off > 0; off >>= 1) {
+#pragma unroll
+      for (int kk = 0; kk < off; ++kk) {
+        p0[w * KK + kk] += p0[w * KK + kk + off];
+        p1[w * KK + kk] += p1[w * KK + kk + off];
+      }
+    }
+    red[((0 * 4 + w) * RG + rg) * CH + ch] = p0[w * KK];
+    red[((1 * 4 + w) * RG + rg) * CH + ch] = p1[w * KK];
+  }
+  __syncthreads();
+  if (threadIdx.x < 8 * CH) { // one thread per (stat, wave, channel)
+    const int q = threadIdx.x / CH;
+    float v[RG];
+#pragma unroll
+    for (int r = 0; r < RG; ++r) v[r] = red[(q * RG + r) * CH + ch];
+#pragma unroll
+    for (int off = RG / 2; off > 0; off >>= 1) {
+#pragma unroll
+      for (int r = 0; r < off; ++r) v[r] += v[r + off];
+    }
+    red2[q * CH + ch] = v[0];
+  }
+  __syncthreads();
+  if (threadIdx.x >= CH || c >= C) return false;
+  r0 = red2[0 * CH + ch] + red2[1 * CH + ch] + red2[2 * CH + ch] +
+       red2[3 * CH + ch];
+  r1 = red2[4 * CH + ch] + red2[5 * CH + ch] + red2[6 * CH + ch] +
+       red2[7 * CH + ch];
+  return true;
+}
+
+// The per-channel epilogues below restate the bands kernels' with the
+// roundings spelled as the parent build compiles them (var and shift are one
+// fma each, the running statistics two rounded products added).
+template <int CH>
+__global__ void __launch_bounds__(256) bn_finalize_fwd_co_k(
+    const float *__restrict__ partial, int grid, int C,
+    const float *__restrict__ gamma, const float *__restrict__ beta,
+    float inv_m, float eps, float *__restrict__ mean,
+    float *__restrict__ invstd, float *__restrict__ scale,
+    float *__restrict__ shift, float *__restrict__ running_mean,
+    float *__restrict__ running_var, float momentum, float unbias) {
+  const int c = blockIdx.x * CH + threadIdx.x;
+  // per-channel loads issue before the slab loop
+  float ga = 0.f, be = 0.f, rm = 0.f, rv = 0.f;
+  if (threadIdx.x < CH && c < C) {
+    ga = gamma[c];
+    be = beta[c];
+    if (running_mean) {
+      rm = running_mean[c];
+      rv = running_var[c];
+    }
+  }
+  float s, sq;
+  if (!bn_fin_co_sums<CH>(partial, grid, C, s, sq)) return;
+  float mu = __fmul_rn(s, inv_m);
+  float var = fmaxf(__fmaf_rn(-mu, mu, __fmul_rn(sq, inv_m)), 0.f);
+  float is = rsqrtf(__fadd_rn(var, eps));
+  mean[c] = mu;
+  invstd[c] = is;
+  float sc = __fmul_rn(ga, is);
+  scale[c] = sc;
+  shift[c] = __fmaf_rn(-mu, sc, be);
+  if (running_mean) {
+    float keep = __fsub_rn(1.f, momentum);
+    running_mean[c] =
+        __fadd_rn(__fmul_rn(rm, keep), __fmul_rn(mu, momentum));
+    running_var[c] = __fadd_rn(
+        __fmul_rn(rv, keep), __fmul_rn(__fmul_rn(var, unbias), momentum));
+  }
+}
+
+template <int CH>
+__global__ void __launch_bounds__(256) bn_finalize_bwd_co_k(
+    const float *__restrict__ partial, int grid, int C,
+    const float *__restrict__ gamma, const float *__restrict__ invstd,
+    float inv_m, float *__restrict__ dbeta, float *__restrict__ dgamma,
+    float *__restrict__ k1, float *__restrict__ k2, float *__restrict__ k3) {
+  const int c = blockIdx.x * CH + threadIdx.x;
+  float ga = 0.f, iv = 0.f;
+  if (threadIdx.x < CH && c < C) {
+    ga = gamma[c];
+    iv = invstd[c];
+  }
+  float s0, s1;
+  if (!bn_fin_co_sums<CH>(partial, grid, C, s0, s1)) return;
+  dbeta[c] = s0;
+  dgamma[c] = s1;
+  float g_is = __fmul_rn(ga, iv);
+  k1[c] = g_is;
+  k2[c] = __fmul_rn(__fmul_rn(g_is, s0), inv_m);
+  k3[c] = __fmul_rn(__fmul_rn(g_is, s1), inv_m);
+}
+
+// Process-wide switches, set through the extension's set_bn_pipelined() and
+// set_bn_finalize_coalesced(); the Python side owns MPIAMD_BN_PIPELINED and
+// MPIAMD_BN_FINALIZE_COALESCED and calls these once at load.
+static std::atomic<bool> g_bn_pipelined{true};
+static std::atomic<bool> g_bn_finalize_co{true};
+static std::atomic<int> g_bn_finalize_ch{0}; // 0: bn_fin_ch()'s table
+
+extern "C" int bn_set_pipelined(int on) {
+  return g_bn_pipelined.exchange(on != 0) ? 1 : 0;
+}
+extern "C" int bn_set_finalize_coalesced(int on) {
+  return g_bn_finalize_co.exchange(on != 0) ? 1 : 0;
+}
+// tools/bn_bench.py's lever: force the slice width (8 or 16) or the bands
+// kernel (-1); 0 restores the table. Returns the previous value.
+extern "C" int bn_set_finalize_ch(int ch) {
+  if (ch != 0 && ch != -1 && ch != 8 && ch != 16) return -2;
+  return g_bn_finalize_ch.exchange(ch);
+}
+
+// The pipelined producers address every tensor with 32-bit byte offsets (16 B
+// per channel group at most) and need BN_OOB past every extent. They pay
+// where a thread runs more than two pair-iterations (M > 2 steps of
+// 2·grid·rows_per_block rows); below that there is nothing left to overlap
+// and the longer prologue costs 4-20 % (tools/bn_bench.py).
+static bool bn_pipe_ok(long M, int C8, int grid, int rows_per_block) {
+  return g_bn_pipelined.load(std::memory_order_relaxed) &&
+         M * C8 * 16 < (1L << 31) && M > 4L * grid * rows_per_block;
+}
+
+// Slice width per (channel count, slab rows), from tools/bn_bench.py
+// (profiles/BENCH_HISTORY.md); 0 keeps the bands kernel for that class: below
+// 256 channels C/CH blocks are too few and the bands kernel is as fast or
+// faster. A width of 32 (whole 128 B lines) lost to 8 and 16 everywhere, its
+// 64 loads per thread serialise, and has no instantiation.
+static int bn_fin_ch(int C, int grid) {
+  if (!g_bn_finalize_co.load(std::memory_order_relaxed)) return 0;
+  if ((long)grid * 2 * C * 4 >= (1L << 31)) return 0;
+  int forced = g_bn_finalize_ch.load(std::memory_order_relaxed);
+  if (forced) return forced < 0 ? 0 : forced;
+  if (C < 256) return 0;
+  return C >= 2048 || (C >= 512 && grid > 1024) ? 16 : 8;
+}
+
+static void bn_finalize_fwd_dispatch(
+    const float *partial, int grid, int C, const float *gamma,
+    const float *beta, float inv_m, float eps, float *mean, float *invstd,
+    float *scale, float *shift, float *running_mean, float *running_var,
+    float momentum, float unbias, hipStream_t s) {
+#define BN_FIN_FWD(CH)                                                         \
+  bn_finalize_fwd_co_k<CH><<<(C + CH - 1) / CH, 256, 0, s>>>(                  \
+      partial, grid, C, gamma, beta, inv_m, eps, mean, invstd, scale, shift,   \
+      running_mean, running_var, momentum, unbias)
+  switch (bn_fin_ch(C, grid)) {
+  case 8: BN_FIN_FWD(8); break;
+  case 16: BN_FIN_FWD(16); break;
+  default:
+    bn_finalize_fwd_bands_k<<<C, 256, 0, s>>>(
+        partial, grid, C, gamma, beta, inv_m, eps, mean, invstd, scale, shift,
+        running_mean, running_var, momentum, unbias);
+  }
+#undef BN_FIN_FWD
+}
+
+static void bn_finalize_bwd_dispatch(const float *partial, int grid, int C,
+                                     const float *gamma, const float *invstd,
+                                     float inv_m, float *dbeta, float *dgamma,
+                                     float *k1, float *k2, float *k3,
+                                     hipStream_t s) {
+#define BN_FIN_BWD(CH)                                                         \
+  bn_finalize_bwd_co_k<CH><<<(C + CH - 1) / CH, 256, 0, s>>>(                  \
+      partial, grid, C, gamma, invstd, inv_m, dbeta, dgamma, k1, k2, k3)
+  switch (bn_fin_ch(C, grid)) {
+  case 8: BN_FIN_BWD(8); break;
+  case 16: BN_FIN_BWD(16); break;
+  default:
+    bn_finalize_bwd_bands_k<<<C, 256, 0, s>>>(partial, grid, C, gamma, invstd,
+                                              inv_m, dbeta, dgamma, k1, k2, k3);
+  }
+#undef BN_FIN_BWD
+}
+
 // partials grid, capped by knobs.h bn_grid_cap()
 static void bn_geom(long M, int C8, int &grid, int &rows_per_block) {
   rows_per_block = 256 / C8;
@@ -671,9 +1163,9 @@ extern "C" hipError_t bn_fwd_train_launch(
                                         C8, 0);
   HIP_KERNEL_CHECK();
   float unbias = M > 1 ? (float)M / (float)(M - 1) : 1.f;
-  bn_finalize_fwd_bands_k<<<C, 256, 0, s>>>(
-      partial, grid, C, gamma, beta, 1.f / (float)M, eps, mean, invstd, scale,
-      shift, running_mean, running_var, momentum, unbias);
+  bn_finalize_fwd_dispatch(partial, grid, C, gamma, beta, 1.f / (float)M, eps,
+                           mean, invstd, scale, shift, running_mean,
+                           running_var, momentum, unbias, s);
   HIP_KERNEL_CHECK();
   bn_apply_k<<<bn_apply_grid(M, C8), 256, 0, s>>>(
       (const ushort8 *)x, (const ushort8 *)res, scale, shift, (ushort8 *)y,
@@ -747,9 +1239,9 @@ extern "C" hipError_t bn_fwd_train_pre_launch(
   int C8 = C / 8;
   if (C8 < 1 || C8 > 256) return hipErrorInvalidValue;
   float unbias = M > 1 ? (float)M / (float)(M - 1) : 1.f;
-  bn_finalize_fwd_bands_k<<<C, 256, 0, s>>>(
-      pre_partial, pre_grid, C, gamma, beta, 1.f / (float)M, eps, mean,
-      invstd, scale, shift, running_mean, running_var, momentum, unbias);
+  bn_finalize_fwd_dispatch(pre_partial, pre_grid, C, gamma, beta,
+                           1.f / (float)M, eps, mean, invstd, scale, shift,
+                           running_mean, running_var, momentum, unbias, s);
   HIP_KERNEL_CHECK();
   bn_apply_k<<<bn_apply_grid(M, C8), 256, 0, s>>>(
       (const ushort8 *)x, (const ushort8 *)res, scale, shift, (ushort8 *)y,
@@ -783,12 +1275,17 @@ extern "C" hipError_t bn_bwd_launch(const void *dy, const void *x,
   if (C8 < 1 || C8 > 256) return hipErrorInvalidValue;
   int grid, rpb;
   bn_geom(M, C8, grid, rpb);
-  bn_partials_k<1><<<grid, 256, 0, s>>>((const ushort8 *)x, (const ushort8 *)dy,
-                                        (const ushort8 *)y, relu_mask, mean,
-                                        invstd, partial, M, C8, relu);
+  if (relu && relu_mask && bn_pipe_ok(M, C8, grid, rpb))
+    bn_partials_bwd_pipe_k<<<grid, 256, 0, s>>>(
+        (const ushort8 *)x, (const ushort8 *)dy, relu_mask, mean, invstd,
+        partial, M, C8);
+  else
+    bn_partials_k<1><<<grid, 256, 0, s>>>((const ushort8 *)x, (const ushort8 *)dy,
+                                          (const ushort8 *)y, relu_mask, mean,
+                                          invstd, partial, M, C8, relu);
   HIP_KERNEL_CHECK();
-  bn_finalize_bwd_bands_k<<<C, 256, 0, s>>>(
-      partial, grid, C, gamma, invstd, 1.f / (float)M, dbeta, dgamma, k1, k2, k3);
+  bn_finalize_bwd_dispatch(partial, grid, C, gamma, invstd, 1.f / (float)M,
+                           dbeta, dgamma, k1, k2, k3, s);
   HIP_KERNEL_CHECK();
   bn_bwd_apply_k<<<bn_apply_grid(M, C8), 256, 0, s>>>(
       (const ushort8 *)dy, (const ushort8 *)x, (const ushort8 *)y, relu_mask,
@@ -868,11 +1365,18 @@ extern "C" hipError_t bn_join_stats_launch(
   if (xd && (!mean_d || !invstd_d || !partial_d)) return hipErrorInvalidValue;
   int grid, rpb;
   bn_geom(M, C8, grid, rpb);
-#define BN_JS_LAUNCH(JOIN, NSTAT)                                              \
-  bn_join_stats_k<JOIN, NSTAT><<<grid, 256, 0, s>>>(                           \
-      (const ushort8 *)a, jmask, (const ushort8 *)b, (ushort8 *)dxt, cmask,    \
+  const bool pipe = jmask && bn_pipe_ok(M, C8, grid, rpb); // JOIN 1 only
+#define BN_JS_ARGS                                                             \
+  (const ushort8 *)a, jmask, (const ushort8 *)b, (ushort8 *)dxt, cmask,        \
       (const ushort8 *)x, mean, invstd, partial, (const ushort8 *)xd, mean_d,  \
-      invstd_d, partial_d, M, C8)
+      invstd_d, partial_d, M, C8
+#define BN_JS_LAUNCH(JOIN, NSTAT)                                              \
+  do {                                                                         \
+    if (pipe)                                                                  \
+      bn_join_stats_pipe_k<NSTAT><<<grid, 256, 0, s>>>(BN_JS_ARGS);            \
+    else                                                                       \
+      bn_join_stats_k<JOIN, NSTAT><<<grid, 256, 0, s>>>(BN_JS_ARGS);           \
+  } while (0)
   if (jmask) {
     if (xd) BN_JS_LAUNCH(1, 2);
     else BN_JS_LAUNCH(1, 1);
@@ -881,6 +1385,7 @@ extern "C" hipError_t bn_join_stats_launch(
     else BN_JS_LAUNCH(0, 1);
   }
 #undef BN_JS_LAUNCH
+#undef BN_JS_ARGS
   return hipGetLastError();
 }
 
@@ -894,9 +1399,8 @@ extern "C" hipError_t bn_bwd_pre_launch(
     hipStream_t s) {
   int C8 = C / 8;
   if (C8 < 1 || C8 > 256) return hipErrorInvalidValue;
-  bn_finalize_bwd_bands_k<<<C, 256, 0, s>>>(pre_partial, pre_grid, C, gamma,
-                                            invstd, 1.f / (float)M, dbeta,
-                                            dgamma, k1, k2, k3);
+  bn_finalize_bwd_dispatch(pre_partial, pre_grid, C, gamma, invstd,
+                           1.f / (float)M, dbeta, dgamma, k1, k2, k3, s);
   HIP_KERNEL_CHECK();
   bn_bwd_apply_k<<<bn_apply_grid(M, C8), 256, 0, s>>>(
       (const ushort8 *)dy, (const ushort8 *)x, (const ushort8 *)y, relu_mask,

@@ -1485,6 +1485,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // previous value (A/B lever and the tests' scalar reference)
   m.def("set_epilogue_vec",
         [](bool on) { return gemm_set_epilogue_vec(on ? 1 : 0) != 0; });
+  // software-pipelined BN statistics producers / line-coalesced BN finalize
+  // on/off for the whole process; each returns the previous value (A/B
+  // levers and the tests' reference: the kernels they replace)
+  m.def("set_bn_pipelined",
+        [](bool on) { return bn_set_pipelined(on ? 1 : 0) != 0; });
+  m.def("set_bn_finalize_coalesced",
+        [](bool on) { return bn_set_finalize_coalesced(on ? 1 : 0) != 0; });
+  // finalize slice width override for tools/bn_bench.py: 0 the built-in
+  // table, -1 the bands kernel, 8 or 16 that width; returns the previous one
+  m.def("set_bn_finalize_ch", [](int ch) {
+    int prev = bn_set_finalize_ch(ch);
+    TORCH_CHECK(prev != -2, "set_bn_finalize_ch: ch must be 0, -1, 8 or 16");
+    return prev;
+  });
   // does the fc2-dx GEMM of dy [M][K] · w2 [K][N] take the transpose-plus-
   // pipe256 route (MPIAMD_GELUBWD_WT)? The route's own predicate.
   m.def("gelubwd_wt_route", [](int M, int N, int K) {

@@ -82,6 +82,12 @@ hipError_t bn_bwd_launch(const void *dy, const void *x, const void *y,
                          float *k2, float *k3, float *partial, long M, int C,
                          hipStream_t s);
 int bn_stats_grid(long M, int C);
+// process-wide A/B switches (each returns the previous value): pipelined
+// statistics producers, line-coalesced finalize, and the finalize slice width
+// override tools/bn_bench.py uses (0 table, -1 bands, 8 or 16; -2 = rejected)
+int bn_set_pipelined(int on);
+int bn_set_finalize_coalesced(int on);
+int bn_set_finalize_ch(int ch);
 hipError_t bn_reduce_stats_fwd_launch(const float *slabs, int splits, void *y,
                                       float *partial, long M, int C,
                                       hipStream_t s);
