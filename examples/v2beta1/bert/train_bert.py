@@ -36,16 +36,23 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="per-GPU sequences")
     ap.add_argument("--seq", type=int, default=128)
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lamb"])
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="hidden-state dropout (published recipes use 0.1)")
+    ap.add_argument("--seed", type=int, default=0,
+                    help="dropout seed; each rank adds its rank")
     args = ap.parse_args()
 
     hvd.init()
     use_cuda = torch.cuda.is_available()
     device = f"cuda:{hvd.local_rank()}" if use_cuda else "cpu"
 
-    model = bert_large() if args.model == "bert_large" else bert_base()
+    model = (bert_large if args.model == "bert_large" else bert_base)(args.dropout)
     if use_cuda:
         model = to_mi355x_bert(model, device)
     model.train()
+    # per-rank masks: the state is not a buffer, so broadcast_parameters
+    # below leaves it alone
+    model.seed_dropout(args.seed + hvd.rank())
     if args.optimizer == "sgd":
         opt = FusedSGD(model.parameters(), lr=1e-4, momentum=0.9)
     elif args.optimizer == "adamw":

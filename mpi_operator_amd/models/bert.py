@@ -58,6 +58,15 @@ class LayerNorm(nn.Module):
                             self.bias.float(), self.eps).to(x.dtype)
 
 
+def _dropout(x, p, rng, site):
+    """Hidden-state dropout at one call site: the Philox HIP kernel for GPU
+    bf16 (masks from the model's DropoutRng), torch's generator otherwise —
+    the same semantics without bit-compatibility."""
+    if rng is not None and x.is_cuda and x.dtype == torch.bfloat16:
+        return Fx.dropout(x, p, rng, site)
+    return F.dropout(x, p, training=True)
+
+
 @dataclass
 class BertConfig:
     vocab_size: int = 30522
@@ -67,16 +76,22 @@ class BertConfig:
     intermediate: int = 4096
     max_seq: int = 512
     type_vocab: int = 2
-    dropout: float = 0.0  # benchmarks run dropout-free (synthetic data)
+    # Hidden-state dropout, applied in train() at three kinds of site: after
+    # the embedding LayerNorm, and on the attention-output and FFN-output
+    # branches ahead of their residual joins. Dropout on the attention
+    # probabilities is not implemented (it belongs inside the attention
+    # kernels). 0.0 = none: benchmarks run dropout-free (synthetic data).
+    dropout: float = 0.0
     eps: float = 1e-12
 
 
-def bert_large() -> "BertForPreTraining":
-    return BertForPreTraining(BertConfig())
+def bert_large(dropout: float = 0.0) -> "BertForPreTraining":
+    return BertForPreTraining(BertConfig(dropout=dropout))
 
 
-def bert_base() -> "BertForPreTraining":
-    return BertForPreTraining(BertConfig(hidden=768, layers=12, heads=12, intermediate=3072))
+def bert_base(dropout: float = 0.0) -> "BertForPreTraining":
+    return BertForPreTraining(BertConfig(hidden=768, layers=12, heads=12, intermediate=3072,
+                                         dropout=dropout))
 
 
 class BertLinear(nn.Module):
@@ -146,16 +161,27 @@ class BertLayer(nn.Module):
         self.fc2 = BertLinear(cfg.intermediate, cfg.hidden)
         self.ln2 = LayerNorm(cfg.hidden, eps=cfg.eps)
 
-    def _join_ln(self, ln, a, b):
-        """residual + LN; fused single-pass kernel when enabled."""
+    def _join_ln(self, ln, a, b, p=0.0, rng=None, site=0):
+        """residual + LN; fused single-pass kernel when enabled. p > 0 drops
+        out the branch b first: inside the join kernel on the fused path."""
+        if p > 0:
+            if (_FUSED_LN and rng is not None and a.is_cuda
+                    and a.dtype == torch.bfloat16):
+                return Fx.layer_norm_drop_add(a, b, ln.weight.float(),
+                                              ln.bias.float(), ln.eps, p, rng,
+                                              site)
+            b = _dropout(b, p, rng, site)
         if _FUSED_LN and a.is_cuda and a.dtype == torch.bfloat16:
             return Fx.layer_norm_add(a, b, ln.weight.float(), ln.bias.float(),
                                      ln.eps)
         return ln(a + b)
 
-    def forward(self, x, attn_mask=None):
+    def forward(self, x, attn_mask=None, p=0.0, rng=None, site=0):
+        """p, rng, site: BertModel's hidden-state dropout for this call
+        (p = 0 outside training); the attention-output join draws at `site`,
+        the FFN-output join at `site + 1`."""
         if (x.is_cuda and x.dtype == torch.bfloat16 and attn_mask is None
-                and self.attn.head_dim == 64 and x.shape[1] == 128
+                and self.attn.head_dim == 64 and x.shape[1] == 128 and p == 0
                 and _os.environ.get("MPIAMD_LAYER_FUSED", "0") == "1"):
             # whole-layer composite Function (Fx.BertLayerFn): residual-join
             # backward adds fold into accumulate-dgrad GEMM epilogues.
@@ -174,7 +200,7 @@ class BertLayer(nn.Module):
                 self.fc2.weight, self.fc2.bias,
                 self.ln2.weight.float(), self.ln2.bias.float())
             return y.view(b, s, h)
-        x = self._join_ln(self.ln1, x, self.attn(x, attn_mask))
+        x = self._join_ln(self.ln1, x, self.attn(x, attn_mask), p, rng, site)
         if x.is_cuda and x.dtype == torch.bfloat16:
             # fused FFN: GELU lives in the GEMM epilogues (fwd emits
             # h_pre + gelu(h); bwd's fc2-dx multiplies by gelu'(h_pre))
@@ -184,7 +210,7 @@ class BertLayer(nn.Module):
                        self.fc2.weight, self.fc2.bias).view(b, s, h)
         else:
             y = self.fc2(F.gelu(self.fc1(x), approximate="tanh"))
-        return self._join_ln(self.ln2, x, y)
+        return self._join_ln(self.ln2, x, y, p, rng, site + 1)
 
 
 class BertEmbeddings(nn.Module):
@@ -197,13 +223,14 @@ class BertEmbeddings(nn.Module):
         for e in (self.tok, self.pos, self.typ):
             nn.init.normal_(e.weight, std=0.02)
 
-    def forward(self, ids, type_ids=None):
+    def forward(self, ids, type_ids=None, p=0.0, rng=None, site=0):
         s = ids.shape[1]
         pos = torch.arange(s, device=ids.device)
         x = self.tok(ids) + self.pos(pos)[None]
         if type_ids is not None:
             x = x + self.typ(type_ids)
-        return self.ln(x)
+        x = self.ln(x)
+        return _dropout(x, p, rng, site) if p > 0 else x
 
 
 class BertModel(nn.Module):
@@ -212,14 +239,62 @@ class BertModel(nn.Module):
         self.cfg = cfg
         self.embeddings = BertEmbeddings(cfg)
         self.layers = nn.ModuleList(BertLayer(cfg) for _ in range(cfg.layers))
+        # Device random-number state of the dropout kernels. A plain
+        # attribute, NOT a buffer: broadcast_parameters would hand every rank
+        # rank 0's seed, and a persistent buffer would change state_dict.
+        self._dropout_rng = None
+        self._dropout_seed = None
+
+    def seed_dropout(self, seed: int):
+        """(Re-)seed the dropout masks and restart their step counter; give
+        each data-parallel rank its own seed. Without it the state is created
+        on the first eager training forward from torch.initial_seed(). On
+        the CPU (or in another dtype than bf16) dropout draws from torch's
+        generator, which this leaves alone; the seed is kept for the GPU."""
+        self._dropout_seed = int(seed)
+        dev = self.embeddings.tok.weight.device
+        rng = self._dropout_rng
+        if rng is not None and rng.state.device == dev:
+            rng.set_state(seed, 0)
+        elif dev.type == "cuda":
+            self._dropout_rng = Fx.DropoutRng(seed, dev)
+        else:
+            self._dropout_rng = None  # created once the model is on a GPU
+
+    def _rng(self, device):
+        rng = self._dropout_rng
+        if rng is None or rng.state.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(
+                    "BertModel: the first training forward with dropout allocates "
+                    "the random-number state and must not run under graph "
+                    "capture; run one eager step first")
+            seed = self._dropout_seed
+            rng = Fx.DropoutRng(torch.initial_seed() if seed is None else seed,
+                                device)
+            self._dropout_rng = rng
+        return rng
 
     def forward(self, ids, type_ids=None, attn_mask=None):
         if attn_mask is not None and attn_mask.dim() == 2:
             # (b, s) 1/0 mask → additive (b, 1, 1, s)
             attn_mask = (1.0 - attn_mask[:, None, None, :].float()) * torch.finfo(torch.float32).min
-        x = self.embeddings(ids, type_ids)
-        for layer in self.layers:
-            x = layer(x, attn_mask)
+        p = self.cfg.dropout if self.training else 0.0
+        if not p > 0:
+            x = self.embeddings(ids, type_ids)
+            for layer in self.layers:
+                x = layer(x, attn_mask)
+            return x
+        # static call sites: embeddings 0, layer i attention-output join
+        # 1 + 2i, FFN-output join 2 + 2i; one tick per forward separates steps
+        rng = None
+        w = self.embeddings.tok.weight
+        if w.is_cuda and w.dtype == torch.bfloat16:
+            rng = self._rng(w.device)
+            rng.tick()
+        x = self.embeddings(ids, type_ids, p, rng, 0)
+        for i, layer in enumerate(self.layers):
+            x = layer(x, attn_mask, p, rng, 1 + 2 * i)
         return x
 
 
@@ -235,6 +310,10 @@ class BertForPreTraining(nn.Module):
         # decoder tied to token embeddings (standard BERT weight tying)
         self.mlm_bias = nn.Parameter(torch.zeros(cfg.vocab_size))
         self.nsp = BertLinear(cfg.hidden, 2)
+
+    def seed_dropout(self, seed: int):
+        """BertModel.seed_dropout of the trunk."""
+        self.bert.seed_dropout(seed)
 
     def forward(self, ids, type_ids=None, attn_mask=None, mlm_labels=None,
                 nsp_labels=None):

@@ -20,7 +20,7 @@ HIPCC = os.environ.get("HIPCC", "hipcc")
 
 KERNEL_SRCS = ["elementwise.hip", "batchnorm.hip", "pooling.hip",
                "softmax_xent.hip", "masked_xent.hip", "attention.hip", "flash_attention.hip", "gemm.hip", "conv.hip", "layernorm.hip",
-               "optimizer.hip"]
+               "optimizer.hip", "dropout.hip"]
 BINDING_SRC = "bindings.cpp"
 
 BASE_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",

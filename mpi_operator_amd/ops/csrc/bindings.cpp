@@ -13,6 +13,7 @@
 
 #include "knobs.h"
 #include "launchers.h"
+#include "philox.h"
 
 namespace {
 
@@ -764,6 +765,164 @@ static std::vector<Tensor> layernorm_bwd(const Tensor &dy, const Tensor &x,
              partial.data_ptr<float>(), dgb.data_ptr<float>(), M, N, nullptr,
              cur_stream()));
   return {dx, dgb.narrow(0, 0, N), dgb.narrow(0, N, N)};
+}
+
+// ------------------------- dropout -------------------------
+// The device random-number state of philox.h: int64 (seed, offset)
+static void check_rng_state(const Tensor &state, const Tensor &like) {
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kLong &&
+                  state.is_contiguous() && state.dim() == 1 &&
+                  state.numel() == 2,
+              "state must be a contiguous int64 [2] GPU tensor (seed, offset)");
+  TORCH_CHECK(state.device() == like.device(), "state is on another device");
+}
+
+struct DropParams {
+  uint32_t site, thr;
+  float scale;
+};
+static DropParams check_drop_params(double p, int64_t site) {
+  DropParams d;
+  TORCH_CHECK(dropout_thr_scale(p, &d.thr, &d.scale),
+              "dropout: p must be in [0, 1) with round(p * 65536) <= 65535, "
+              "got ", p);
+  TORCH_CHECK(site >= 0 && site <= (int64_t)UINT32_MAX,
+              "dropout: site must fit a uint32, got ", site);
+  d.site = (uint32_t)site;
+  return d;
+}
+
+// dense bf16 GPU tensor walked in octets by one Philox call each
+static void check_drop_bf16(const Tensor &t, const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, name,
+              " must be a bf16 GPU tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(dropout_numel_ok(t.numel()), name,
+              ": element count must be a positive multiple of 8 below 2^35, "
+              "got ", t.numel());
+}
+
+static void check_drop_same(const Tensor &t, const Tensor &like,
+                            const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() &&
+                  t.scalar_type() == at::kBFloat16 && t.is_contiguous() &&
+                  t.sizes() == like.sizes(),
+              name, " must be a contiguous bf16 tensor of shape ",
+              like.sizes(), " on the first operand's GPU");
+}
+
+// keep bitmask, one byte per octet, of the given shape
+static void check_keep_mask(const Tensor &mask, at::IntArrayRef shape,
+                            const Tensor &like) {
+  TORCH_CHECK(mask.is_cuda() && mask.device() == like.device() &&
+                  mask.scalar_type() == at::kByte && mask.is_contiguous() &&
+                  mask.sizes() == shape,
+              "mask must be a contiguous uint8 GPU tensor of shape ", shape,
+              " (one byte per 8 elements), got ", mask.sizes());
+}
+
+// fp32 [N] LayerNorm vector on the activation's device
+static void check_ln_vec(const Tensor &t, int64_t n, const Tensor &like,
+                         const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() &&
+                  t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                  t.numel() == n,
+              name, " must be a contiguous fp32 GPU tensor of ", n,
+              " elements");
+}
+
+static void rng_tick_b(const Tensor &state) {
+  check_rng_state(state, state);
+  const HIPDeviceGuard guard(state.device());
+  CHK(rng_tick(state.data_ptr<int64_t>(), cur_stream()));
+}
+
+// y = keep ? x / (1 - p_eff) : 0; returns {y, mask [numel/8] uint8}
+static std::vector<Tensor> dropout_fwd_b(const Tensor &x, const Tensor &state,
+                                         double p, int64_t site) {
+  check_drop_bf16(x, "x");
+  check_rng_state(state, x);
+  const DropParams d = check_drop_params(p, site);
+  const HIPDeviceGuard guard(x.device());
+  Tensor y = at::empty_like(x);
+  Tensor mask = at::empty({x.numel() / 8}, x.options().dtype(at::kByte));
+  CHK(dropout_fwd(x.data_ptr(), state.data_ptr<int64_t>(), d.site, d.thr,
+                  d.scale, y.data_ptr(), mask.data_ptr<uint8_t>(), x.numel(),
+                  cur_stream()));
+  return {y, mask};
+}
+
+static Tensor dropout_bwd_b(const Tensor &dy, const Tensor &mask, double p) {
+  check_drop_bf16(dy, "dy");
+  check_keep_mask(mask, {dy.numel() / 8}, dy);
+  const DropParams d = check_drop_params(p, 0);
+  const HIPDeviceGuard guard(dy.device());
+  Tensor dx = at::empty_like(dy);
+  CHK(dropout_bwd(dy.data_ptr(), mask.data_ptr<uint8_t>(), d.scale,
+                  dx.data_ptr(), dy.numel(), cur_stream()));
+  return dx;
+}
+
+// y = LN(a + dropout(b)); returns {y, s, mean, rstd, mask [M][N/8] uint8}
+static std::vector<Tensor> layernorm_drop_add_fwd(
+    const Tensor &a, const Tensor &b, const Tensor &gamma, const Tensor &beta,
+    double eps, const Tensor &state, double p, int64_t site) {
+  TORCH_CHECK(a.dim() >= 1, "a must have a feature dimension");
+  check_drop_bf16(a, "a");
+  check_drop_same(b, a, "b");
+  const int64_t N = a.size(-1);
+  TORCH_CHECK(N % 8 == 0 && N >= 8,
+              "layernorm_drop_add_fwd: N must be a positive multiple of 8, "
+              "got ", N);
+  check_ln_vec(gamma, N, a, "gamma");
+  check_ln_vec(beta, N, a, "beta");
+  check_rng_state(state, a);
+  const DropParams d = check_drop_params(p, site);
+  const HIPDeviceGuard guard(a.device());
+  const int64_t M = a.numel() / N;
+  auto f32 = a.options().dtype(at::kFloat);
+  Tensor sum = at::empty_like(a);
+  Tensor y = at::empty_like(a);
+  Tensor mean = at::empty({M}, f32), rstd = at::empty({M}, f32);
+  Tensor mask = at::empty({M, N / 8}, a.options().dtype(at::kByte));
+  CHK(ln_fwd_drop_add(a.data_ptr(), b.data_ptr(), gamma.data_ptr<float>(),
+                      beta.data_ptr<float>(), state.data_ptr<int64_t>(),
+                      d.site, d.thr, d.scale, sum.data_ptr(), y.data_ptr(),
+                      mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                      mask.data_ptr<uint8_t>(), M, (int)N, (float)eps,
+                      cur_stream()));
+  return {y, sum, mean, rstd, mask};
+}
+
+// returns {da, db, dgamma, dbeta}: da = dLN/ds, db = da through the mask
+static std::vector<Tensor> layernorm_drop_add_bwd(
+    const Tensor &dy, const Tensor &s, const Tensor &gamma, const Tensor &mean,
+    const Tensor &rstd, const Tensor &mask, double p) {
+  TORCH_CHECK(s.dim() >= 1, "s must have a feature dimension");
+  check_drop_bf16(s, "s");
+  check_drop_same(dy, s, "dy");
+  const int64_t N = s.size(-1);
+  TORCH_CHECK(N % 8 == 0 && N >= 8 && N <= 2048,
+              "layernorm_drop_add_bwd: N must be a multiple of 8 in "
+              "[8, 2048], got ", N);
+  const int64_t M = s.numel() / N;
+  check_ln_vec(gamma, N, s, "gamma");
+  check_ln_vec(mean, M, s, "mean");
+  check_ln_vec(rstd, M, s, "rstd");
+  check_keep_mask(mask, {M, N / 8}, s);
+  const DropParams d = check_drop_params(p, 0);
+  const HIPDeviceGuard guard(s.device());
+  auto f32 = s.options().dtype(at::kFloat);
+  // slab rows must cover ln_bwd's stats grid (≤512 by construction)
+  Tensor partial = at::empty({512, 2L * N}, f32);
+  Tensor dgb = at::empty({2L * N}, f32);
+  Tensor da = at::empty_like(s), db = at::empty_like(s);
+  CHK(ln_bwd_drop(dy.data_ptr(), s.data_ptr(), gamma.data_ptr<float>(),
+                  mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                  mask.data_ptr<uint8_t>(), d.scale, da.data_ptr(),
+                  db.data_ptr(), partial.data_ptr<float>(),
+                  dgb.data_ptr<float>(), M, (int)N, nullptr, cur_stream()));
+  return {da, db, dgb.narrow(0, 0, N), dgb.narrow(0, N, N)};
 }
 
 // ------------------------- linear -------------------------
@@ -1534,6 +1693,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("layernorm_bwd", &layernorm_bwd);
   m.def("layernorm_add_fwd", &layernorm_add_fwd);
+  m.def("rng_tick", &rng_tick_b);
+  m.def("dropout_fwd", &dropout_fwd_b, py::arg("x"), py::arg("state"),
+        py::arg("p"), py::arg("site"));
+  m.def("dropout_bwd", &dropout_bwd_b, py::arg("dy"), py::arg("mask"),
+        py::arg("p"));
+  m.def("layernorm_drop_add_fwd", &layernorm_drop_add_fwd, py::arg("a"),
+        py::arg("b"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
+        py::arg("state"), py::arg("p"), py::arg("site"));
+  m.def("layernorm_drop_add_bwd", &layernorm_drop_add_bwd, py::arg("dy"),
+        py::arg("s"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
+        py::arg("mask"), py::arg("p"));
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_bwd", &linear_bwd);
   m.def("linear_dgrad", &linear_dgrad);

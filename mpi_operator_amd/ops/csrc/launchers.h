@@ -244,6 +244,27 @@ hipError_t ln_bwd(const void *dy, const void *x, const float *gamma,
                   const float *mean, const float *rstd, void *dx,
                   float *partial, float *dgamma_dbeta, long M, int N,
                   int *grid_out, hipStream_t s);
+hipError_t ln_fwd_drop_add(const void *a, const void *b, const float *gamma,
+                           const float *beta, const int64_t *state,
+                           uint32_t site, uint32_t thr, float scale,
+                           void *sum_out, void *y, float *mean, float *rstd,
+                           uint8_t *mask, long M, int N, float eps,
+                           hipStream_t s);
+hipError_t ln_bwd_drop(const void *dy, const void *x, const float *gamma,
+                       const float *mean, const float *rstd,
+                       const uint8_t *mask, float scale, void *da, void *db,
+                       float *partial, float *dgamma_dbeta, long M, int N,
+                       int *grid_out, hipStream_t s);
+
+// ---- dropout.hip ----
+// state: the device (seed, offset) pair of philox.h; thr and scale from
+// dropout_thr_scale(p); mask: one keep byte per octet
+hipError_t rng_tick(int64_t *state, hipStream_t s);
+hipError_t dropout_fwd(const void *x, const int64_t *state, uint32_t site,
+                       uint32_t thr, float scale, void *y, uint8_t *mask,
+                       long n, hipStream_t s);
+hipError_t dropout_bwd(const void *dy, const uint8_t *mask, float scale,
+                       void *dx, long n, hipStream_t s);
 
 // ---- optimizer.hip ----
 int optim_block_count(const OptDesc *descs, int nt);

@@ -631,3 +631,122 @@ class LayerNormAddFn(torch.autograd.Function):
 
 def layer_norm_add(a, b, weight, bias, eps: float = 1e-12):
     return LayerNormAddFn.apply(a, b, weight, bias, eps)
+
+
+class DropoutRng:
+    """Device random-number state of the dropout kernels: an int64 tensor
+    (seed, offset). The kernels read both from device memory on every
+    launch and tick() advances offset with a one-thread kernel, so a train
+    step captured into a graph draws fresh masks on each replay (a seed or
+    offset passed as a launch argument would be frozen at capture) — the
+    optimizers' device step state, applied to random numbers."""
+
+    def __init__(self, seed: int, device):
+        self.state = torch.tensor(self._signed(seed, 0), dtype=torch.int64,
+                                  device=device)
+
+    @staticmethod
+    def _signed(seed: int, offset: int):
+        # any Python int → the int64 bit pattern the kernels read as uint64
+        return [((int(v) + (1 << 63)) % (1 << 64)) - (1 << 63)
+                for v in (seed, offset)]
+
+    def tick(self):
+        """offset += 1 on the device, in stream order (capturable)."""
+        hip_ext().rng_tick(self.state)
+
+    def get_state(self):
+        """(seed, offset) as unsigned 64-bit ints. Synchronizes: not for use
+        under graph capture."""
+        if self.state.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DropoutRng.get_state() synchronizes and must "
+                               "not run under graph capture")
+        seed, offset = (int(v) % (1 << 64) for v in self.state.tolist())
+        return seed, offset
+
+    def set_state(self, seed: int, offset: int):
+        self.state.copy_(torch.tensor(self._signed(seed, offset),
+                                      dtype=torch.int64))
+
+
+def _check_p(p: float) -> None:
+    ref.dropout_threshold(p)  # ValueError outside the kernels' contract
+
+
+class DropoutFn(torch.autograd.Function):
+    """Philox dropout of a contiguous bf16 tensor (csrc/dropout.hip). Saves
+    the keep bitmask (one byte per 8 elements); the backward reads it and
+    never regenerates it. Returns (y, mask)."""
+
+    @staticmethod
+    def forward(ctx, x, p: float, state, site: int):
+        y, mask = hip_ext().dropout_fwd(x, state, p, site)
+        ctx.save_for_backward(mask)
+        ctx.p = p
+        ctx.mark_non_differentiable(mask)
+        ctx.set_materialize_grads(False)
+        return y, mask
+
+    @staticmethod
+    def backward(ctx, dy, _dmask=None):
+        (mask,) = ctx.saved_tensors
+        return hip_ext().dropout_bwd(dy.contiguous(), mask, ctx.p), None, None, None
+
+
+def dropout_with_mask(x, p: float, rng: DropoutRng, site: int):
+    """(y, mask): y = keep ? x / (1 - p_eff) : 0 and the uint8 keep bitmask
+    [numel/8], bit j of byte o = element 8·o + j. p > 0, GPU bf16 only."""
+    _check_p(p)
+    return DropoutFn.apply(x.contiguous(), p, rng.state, site)
+
+
+def dropout(x, p: float, rng: DropoutRng, site: int):
+    """Dropout with masks from the device Philox state `rng` at call site
+    `site` (distinct sites draw independent masks within a step; rng.tick()
+    separates steps). p == 0 is the identity."""
+    _check_p(p)
+    if p == 0:
+        return x
+    return dropout_with_mask(x, p, rng, site)[0]
+
+
+class LayerNormDropAddFn(torch.autograd.Function):
+    """y = LN(a + dropout(b)): LayerNormAddFn with the branch's dropout
+    drawn inside the join kernel (no separate pass over the [M, H]
+    activation); backward writes da and db = da·keep/(1 - p_eff) from one
+    dx kernel off the saved bitmask. Returns (y, mask)."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight, bias, eps: float, p: float, state, site: int):
+        y, s, mean, rstd, mask = hip_ext().layernorm_drop_add_fwd(
+            a, b, weight, bias, eps, state, p, site)
+        ctx.save_for_backward(s, weight, mean, rstd, mask)
+        ctx.p = p
+        ctx.mark_non_differentiable(mask)
+        ctx.set_materialize_grads(False)
+        return y, mask
+
+    @staticmethod
+    def backward(ctx, dy, _dmask=None):
+        s, weight, mean, rstd, mask = ctx.saved_tensors
+        da, db, dg, dbeta = hip_ext().layernorm_drop_add_bwd(
+            dy.contiguous(), s, weight, mean, rstd, mask, ctx.p)
+        return da, db, dg, dbeta, None, None, None, None
+
+
+def layer_norm_drop_add_with_mask(a, b, weight, bias, eps: float, p: float,
+                                  rng: DropoutRng, site: int):
+    """(y, mask) of LayerNormDropAddFn; mask is uint8 [M, N/8]. p > 0."""
+    _check_p(p)
+    return LayerNormDropAddFn.apply(a.contiguous(), b.contiguous(), weight,
+                                    bias, eps, p, rng.state, site)
+
+
+def layer_norm_drop_add(a, b, weight, bias, eps: float = 1e-12, p: float = 0.0,
+                        rng: DropoutRng = None, site: int = 0):
+    """y = LN(a + dropout(b, p)); p == 0 is layer_norm_add itself."""
+    _check_p(p)
+    if p == 0:
+        return layer_norm_add(a, b, weight, bias, eps)
+    return layer_norm_drop_add_with_mask(a, b, weight, bias, eps, p, rng,
+                                         site)[0]

@@ -269,3 +269,72 @@ def flash_attention_bwd(qkv, ctx, dctx, lse, scale: float, mask=None):
     dqkv = torch.stack(
         [dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2)], dim=2)
     return dqkv.to(qkv.dtype)
+
+
+# ---------------------------------------------------------------- dropout
+# The random-number scheme of csrc/philox.h, bit for bit, on the CPU.
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 from its definition. counter: four uint32 values or
+    equal-shaped arrays, key: two uint32 values → the four output words as
+    uint32 arrays. 64-bit products in numpy uint64 (M0*c0 overflows int64)."""
+    import numpy as np
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(v, dtype=np.uint64) & m32 for v in counter]
+    c = list(np.broadcast_arrays(*c))
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0 = np.uint64(PHILOX_M0) * c[0]
+        p1 = np.uint64(PHILOX_M1) * c[2]
+        hi0, lo0 = p0 >> s32, p0 & m32
+        hi1, lo1 = p1 >> s32, p1 & m32
+        c = [hi1 ^ c[1] ^ np.uint64(k0), lo1, hi0 ^ c[3] ^ np.uint64(k1), lo0]
+        k0 = (k0 + PHILOX_W0) & 0xFFFFFFFF  # the key is bumped after each round
+        k1 = (k1 + PHILOX_W1) & 0xFFFFFFFF
+    return [w.astype(np.uint32) for w in c]
+
+
+def dropout_threshold(p: float):
+    """p → (thr, p_eff, scale): thr = round(p·65536) of the 16-bit draw,
+    p_eff = thr/65536, scale = 1/(1 - p_eff) rounded once to fp32.
+    ValueError outside 0 <= p < 1 or where thr would reach 65536."""
+    import numpy as np
+    if not (0.0 <= p < 1.0):
+        raise ValueError(f"dropout probability must be in [0, 1), got {p}")
+    thr = int(round(p * 65536.0))
+    if thr > 65535:
+        raise ValueError(f"dropout probability {p} rounds to 1 (thr = {thr})")
+    p_eff = thr / 65536.0
+    scale = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p_eff)))
+    return thr, p_eff, scale
+
+
+def philox_dropout_mask(seed: int, offset: int, site: int, shape, p: float):
+    """The keep mask (True = kept) the dropout kernels draw for a contiguous
+    tensor of `shape`: key (seed_lo, seed_hi), counter (octet, site,
+    offset_lo, offset_hi) with octet = flat index // 8; element j of the
+    octet takes r_j = (w[j >> 1] >> 16·(j & 1)) & 0xffff, kept iff r_j >= thr."""
+    import numpy as np
+    thr, _, _ = dropout_threshold(p)
+    n = 1
+    for d in shape:
+        n *= int(d)
+    if n % 8 or n // 8 >= 1 << 32:
+        raise ValueError(f"element count {n} must be a multiple of 8 below 2^35")
+    if not 0 <= site < 1 << 32:
+        raise ValueError(f"site {site} does not fit a uint32")
+    seed &= (1 << 64) - 1
+    offset &= (1 << 64) - 1
+    octet = np.arange(n // 8, dtype=np.uint64)
+    w = philox4x32_10(
+        (octet, site, offset & 0xFFFFFFFF, offset >> 32),
+        (seed & 0xFFFFFFFF, seed >> 32))
+    r = np.empty((n // 8, 8), dtype=np.uint32)
+    for j in range(8):
+        r[:, j] = (w[j >> 1] >> np.uint32(16 * (j & 1))) & np.uint32(0xFFFF)
+    keep = r >= np.uint32(thr)
+    return torch.from_numpy(keep.reshape(tuple(int(d) for d in shape)))

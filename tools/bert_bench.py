@@ -25,14 +25,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--graph", type=int, default=1)
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lamb"])
+    ap.add_argument("--dropout", type=float, default=0.0)
+    ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
 
+    from mpi_operator_amd import parallel as hvd
     from mpi_operator_amd.models import bert as B
     from mpi_operator_amd.optim import FusedAdamW, FusedLAMB, FusedSGD
 
     torch.manual_seed(0)
-    m = B.to_mi355x_bert(getattr(B, args.model)(), "cuda")
+    m = B.to_mi355x_bert(getattr(B, args.model)(args.dropout), "cuda")
     m.train()
+    m.seed_dropout(args.seed + hvd.rank())
     if args.optimizer == "sgd":
         opt = FusedSGD(m.parameters(), lr=1e-3, momentum=0.9)
     elif args.optimizer == "adamw":
