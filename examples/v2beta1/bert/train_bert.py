@@ -38,6 +38,9 @@ def main():
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lamb"])
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="hidden-state dropout (published recipes use 0.1)")
+    ap.add_argument("--attn-dropout", type=float, default=0.0,
+                    help="dropout on the attention probabilities (published "
+                         "recipes use 0.1)")
     ap.add_argument("--seed", type=int, default=0,
                     help="dropout seed; each rank adds its rank")
     args = ap.parse_args()
@@ -46,7 +49,8 @@ def main():
     use_cuda = torch.cuda.is_available()
     device = f"cuda:{hvd.local_rank()}" if use_cuda else "cpu"
 
-    model = (bert_large if args.model == "bert_large" else bert_base)(args.dropout)
+    model = (bert_large if args.model == "bert_large" else bert_base)(
+        args.dropout, args.attn_dropout)
     if use_cuda:
         model = to_mi355x_bert(model, device)
     model.train()

@@ -78,20 +78,27 @@ class BertConfig:
     type_vocab: int = 2
     # Hidden-state dropout, applied in train() at three kinds of site: after
     # the embedding LayerNorm, and on the attention-output and FFN-output
-    # branches ahead of their residual joins. Dropout on the attention
-    # probabilities is not implemented (it belongs inside the attention
-    # kernels). 0.0 = none: benchmarks run dropout-free (synthetic data).
+    # branches ahead of their residual joins.
+    # 0.0 = none: benchmarks run dropout-free (synthetic data).
     dropout: float = 0.0
+    # Dropout on the attention probabilities (the fourth site of the
+    # published recipe), applied in train(): drawn inside the attention
+    # kernels on GPU bf16, F.dropout on the eager chain's probs otherwise.
+    attn_dropout: float = 0.0
     eps: float = 1e-12
 
 
-def bert_large(dropout: float = 0.0) -> "BertForPreTraining":
-    return BertForPreTraining(BertConfig(dropout=dropout))
+def bert_large(dropout: float = 0.0,
+               attn_dropout: float = 0.0) -> "BertForPreTraining":
+    return BertForPreTraining(BertConfig(dropout=dropout,
+                                         attn_dropout=attn_dropout))
 
 
-def bert_base(dropout: float = 0.0) -> "BertForPreTraining":
+def bert_base(dropout: float = 0.0,
+              attn_dropout: float = 0.0) -> "BertForPreTraining":
     return BertForPreTraining(BertConfig(hidden=768, layers=12, heads=12, intermediate=3072,
-                                         dropout=dropout))
+                                         dropout=dropout,
+                                         attn_dropout=attn_dropout))
 
 
 class BertLinear(nn.Module):
@@ -123,17 +130,22 @@ class SelfAttention(nn.Module):
         self.out = BertLinear(cfg.hidden, cfg.hidden)
         self.scale = 1.0 / math.sqrt(self.head_dim)
 
-    def forward(self, x, attn_mask=None):
+    def forward(self, x, attn_mask=None, p=0.0, rng=None, site=0):
+        """p, rng, site: dropout on the attention probabilities (p = 0
+        outside training). The HIP kernels draw it themselves from `rng` at
+        `site`; without an rng (CPU, other dtypes) the eager chain applies
+        F.dropout to probs."""
         b, s, h = x.shape
         qkv = self.qkv(x).view(b, s, 3, self.heads, self.head_dim)
-        if (x.is_cuda and x.dtype == torch.bfloat16 and self.head_dim == 64
-                and s <= 256 and attn_mask is None):
+        hip = (x.is_cuda and x.dtype == torch.bfloat16 and self.head_dim == 64
+               and (p == 0 or rng is not None))
+        if hip and s <= 256 and attn_mask is None:
             # fused QKᵀ→softmax→PV kernel (one launch per step instead of
             # the batched-matmul + softmax chain); emits ctx in [b, s, h]
             # directly — no transpose/reshape passes
-            return self.out(Fx.attention(qkv, self.heads, self.scale))
-        if (x.is_cuda and x.dtype == torch.bfloat16 and self.head_dim == 64
-                and (attn_mask is None or attn_mask.shape == (b, 1, 1, s))
+            return self.out(Fx.attention(qkv, self.heads, self.scale, None,
+                                         p, rng, site))
+        if (hip and (attn_mask is None or attn_mask.shape == (b, 1, 1, s))
                 and _os.environ.get("MPIAMD_FLASH_ATTN",
                                     _FLASH_ATTN_DEFAULT) != "0"):
             # tiled online-softmax kernels: s > 256 and/or the additive key
@@ -141,12 +153,15 @@ class SelfAttention(nn.Module):
             # [b, nh, s, s] probs. Other mask shapes keep the eager chain.
             return self.out(Fx.flash_attention(
                 qkv, self.heads, self.scale,
-                attn_mask.reshape(b, s) if attn_mask is not None else None))
+                attn_mask.reshape(b, s) if attn_mask is not None else None,
+                p, rng, site))
         q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # b, nh, s, hd
         scores = torch.matmul(q, k.transpose(-1, -2)) * self.scale
         if attn_mask is not None:
             scores = scores + attn_mask
         probs = torch.softmax(scores.float(), dim=-1).to(v.dtype)
+        if p > 0:
+            probs = F.dropout(probs, p, training=True)
         ctx = torch.matmul(probs, v)  # b, nh, s, hd
         ctx = ctx.transpose(1, 2).reshape(b, s, h)
         return self.out(ctx)
@@ -176,12 +191,15 @@ class BertLayer(nn.Module):
                                      ln.eps)
         return ln(a + b)
 
-    def forward(self, x, attn_mask=None, p=0.0, rng=None, site=0):
+    def forward(self, x, attn_mask=None, p=0.0, rng=None, site=0,
+                attn_p=0.0, attn_site=0):
         """p, rng, site: BertModel's hidden-state dropout for this call
         (p = 0 outside training); the attention-output join draws at `site`,
-        the FFN-output join at `site + 1`."""
+        the FFN-output join at `site + 1`. attn_p, attn_site: dropout on the
+        attention probabilities, drawn from the same rng at `attn_site`."""
         if (x.is_cuda and x.dtype == torch.bfloat16 and attn_mask is None
                 and self.attn.head_dim == 64 and x.shape[1] == 128 and p == 0
+                and attn_p == 0
                 and _os.environ.get("MPIAMD_LAYER_FUSED", "0") == "1"):
             # whole-layer composite Function (Fx.BertLayerFn): residual-join
             # backward adds fold into accumulate-dgrad GEMM epilogues.
@@ -200,7 +218,9 @@ class BertLayer(nn.Module):
                 self.fc2.weight, self.fc2.bias,
                 self.ln2.weight.float(), self.ln2.bias.float())
             return y.view(b, s, h)
-        x = self._join_ln(self.ln1, x, self.attn(x, attn_mask), p, rng, site)
+        x = self._join_ln(
+            self.ln1, x, self.attn(x, attn_mask, attn_p, rng, attn_site), p,
+            rng, site)
         if x.is_cuda and x.dtype == torch.bfloat16:
             # fused FFN: GELU lives in the GEMM epilogues (fwd emits
             # h_pre + gelu(h); bwd's fc2-dx multiplies by gelu'(h_pre))
@@ -280,21 +300,24 @@ class BertModel(nn.Module):
             # (b, s) 1/0 mask → additive (b, 1, 1, s)
             attn_mask = (1.0 - attn_mask[:, None, None, :].float()) * torch.finfo(torch.float32).min
         p = self.cfg.dropout if self.training else 0.0
-        if not p > 0:
+        pa = self.cfg.attn_dropout if self.training else 0.0
+        if not (p > 0 or pa > 0):
             x = self.embeddings(ids, type_ids)
             for layer in self.layers:
                 x = layer(x, attn_mask)
             return x
         # static call sites: embeddings 0, layer i attention-output join
-        # 1 + 2i, FFN-output join 2 + 2i; one tick per forward separates steps
+        # 1 + 2i, FFN-output join 2 + 2i, attention probabilities
+        # 1 + 2·layers + i; one tick per forward separates steps
         rng = None
         w = self.embeddings.tok.weight
         if w.is_cuda and w.dtype == torch.bfloat16:
             rng = self._rng(w.device)
             rng.tick()
+        n = len(self.layers)
         x = self.embeddings(ids, type_ids, p, rng, 0)
         for i, layer in enumerate(self.layers):
-            x = layer(x, attn_mask, p, rng, 1 + 2 * i)
+            x = layer(x, attn_mask, p, rng, 1 + 2 * i, pa, 1 + 2 * n + i)
         return x
 
 

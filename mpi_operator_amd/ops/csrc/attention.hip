@@ -24,6 +24,7 @@
 // ctx is [B, S, H·64] so the consumer (attn.out linear) needs no reshape.
 #include "common.h"
 #include "launchers.h"
+#include "philox.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8a;
 typedef __attribute__((ext_vector_type(4))) float float4a;
@@ -39,13 +40,18 @@ DEV_INLINE bf16x8a us8_to_bf8a(ushort8 u) {
 DEV_INLINE int att_swz(int q, int row) { return q ^ ((row >> 2) & 7); }
 
 // S_MAX: compile-time sequence capacity (LDS sizing); launched per actual S.
-template <int S_MAX>
+// DROP: dropout on P with the attention mask scheme of philox.h. The P image
+// takes keep ? bf16(P) : 0, the fp32 accumulator of P·V is scaled by
+// 1/(1 - p_eff) before the ctx store, and the saved probs keep bf16(P) with
+// the SIGN BIT set where dropped (P >= 0, so the bit is free): the backward
+// needs both P and the mask and gets them from the one tensor.
+template <int S_MAX, bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_k(
     const uint16_t *__restrict__ qkv, // [B, S, 3, H, 64]
     uint16_t *__restrict__ ctx,       // [B, S, H*64]
     uint16_t *__restrict__ probs,     // [B, H, S, S] or nullptr
     const float *__restrict__ mask,   // [B, S] additive (or nullptr)
-    int B, int S, int H, float scale) {
+    int B, int S, int H, float scale, AttnDropArgs da) {
   constexpr int D = 64;
   int bh = blockIdx.x;
   int b = bh / H, h = bh % H;
@@ -161,6 +167,17 @@ __global__ __launch_bounds__(256) void attn_fwd_k(
     srow[r] = 1.f / s;
   }
 
+  // keep bits of this lane's 16 registers per column fragment (two Philox
+  // calls each); columns >= S hold P = 0 whatever they draw
+  uint32_t kb[NF];
+  if (DROP) {
+    AttnDrop dr = attn_drop_init(da, bh, S);
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni)
+      kb[ni] = attn_drop_keep16(dr, (uint32_t)qrow0 >> 4, lane >> 5,
+                                ni * 32 + (lane & 31));
+  }
+
   // normalize + park P in this wave's LDS image (and optionally to global)
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -169,9 +186,15 @@ __global__ __launch_bounds__(256) void attn_fwd_k(
     for (int ni = 0; ni < NF; ++ni) {
       int col = ni * 32 + (lane & 31);
       uint16_t pv = f2bf(acc[ni][r] * srow[r]);
+      uint16_t sv = pv; // as saved
+      if (DROP) {
+        bool keep = (kb[ni] >> r) & 1u;
+        sv = keep ? pv : (uint16_t)(pv | 0x8000u);
+        pv = keep ? pv : (uint16_t)0;
+      }
       p_img[wave][prow][col] = pv;
       if (probs && col < S && qrow0 + prow < S)
-        probs[((long)bh * S + qrow0 + prow) * S + col] = pv;
+        probs[((long)bh * S + qrow0 + prow) * S + col] = sv;
     }
   }
   // P image is per-wave private; the producing lanes and consuming lanes
@@ -222,28 +245,50 @@ __global__ __launch_bounds__(256) void attn_fwd_k(
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
       int d = ni * 32 + (lane & 31);
-      cp[(long)row * crow + d] = f2bf(oacc[ni][r]);
+      cp[(long)row * crow + d] =
+          f2bf(DROP ? oacc[ni][r] * da.rs : oacc[ni][r]);
     }
   }
+}
+
+template <bool DROP>
+static hipError_t attn_fwd_dispatch(const void *qkv, void *ctx, void *probs,
+                                    const float *mask, int B, int S, int H,
+                                    float scale, AttnDropArgs da,
+                                    hipStream_t strm) {
+  // LDS: S_MAX=128 → 64 KiB (2 blocks/CU); S_MAX=256 → 128 KiB (1/CU).
+  // S > 256 needs a tiled/online-softmax variant (flash_attention.hip).
+  if (S <= 128)
+    attn_fwd_k<128, DROP><<<dim3(B * H, 1), 256, 0, strm>>>(
+        (const uint16_t *)qkv, (uint16_t *)ctx, (uint16_t *)probs, mask, B, S,
+        H, scale, da);
+  else if (S <= 256) // two 128-row q-chunks per (b, h)
+    attn_fwd_k<256, DROP><<<dim3(B * H, 2), 256, 0, strm>>>(
+        (const uint16_t *)qkv, (uint16_t *)ctx, (uint16_t *)probs, mask, B, S,
+        H, scale, da);
+  else
+    return hipErrorInvalidValue;
+  HIP_KERNEL_CHECK();
+  return hipSuccess;
 }
 
 extern "C" hipError_t attn_fwd_launch(const void *qkv, void *ctx, void *probs,
                                       const float *mask, int B, int S, int H,
                                       float scale, hipStream_t strm) {
-  // LDS: S_MAX=128 → 64 KiB (2 blocks/CU); S_MAX=256 → 128 KiB (1/CU).
-  // S > 256 needs a tiled/online-softmax variant (torch fallback upstream).
-  if (S <= 128)
-    attn_fwd_k<128><<<dim3(B * H, 1), 256, 0, strm>>>(
-        (const uint16_t *)qkv, (uint16_t *)ctx, (uint16_t *)probs, mask, B, S,
-        H, scale);
-  else if (S <= 256) // two 128-row q-chunks per (b, h)
-    attn_fwd_k<256><<<dim3(B * H, 2), 256, 0, strm>>>(
-        (const uint16_t *)qkv, (uint16_t *)ctx, (uint16_t *)probs, mask, B, S,
-        H, scale);
-  else
-    return hipErrorInvalidValue;
-  HIP_KERNEL_CHECK();
-  return hipSuccess;
+  return attn_fwd_dispatch<false>(qkv, ctx, probs, mask, B, S, H, scale,
+                                  AttnDropArgs{}, strm);
+}
+
+// probs is required: it carries the mask to the backward
+extern "C" hipError_t attn_drop_fwd_launch(const void *qkv, void *ctx,
+                                           void *probs, const float *mask,
+                                           const int64_t *state, uint32_t site,
+                                           uint32_t thr, float rs, int B,
+                                           int S, int H, float scale,
+                                           hipStream_t strm) {
+  if (!probs || !state) return hipErrorInvalidValue;
+  return attn_fwd_dispatch<true>(qkv, ctx, probs, mask, B, S, H, scale,
+                                 AttnDropArgs{state, site, thr, rs}, strm);
 }
 
 // ---- fused attention backward (S == 128, D == 64) ---------------------
@@ -257,12 +302,18 @@ extern "C" hipError_t attn_fwd_launch(const void *qkv, void *ctx, void *probs,
 // ds_read_b64_tr_b16); dS lives in ONE such image that serves both the
 // k-contiguous dQ reads (b128 at subtile-linear addresses) and the
 // k-strided dK reads (tr pairs).
+// DROP: probs is the forward's sign-coded tensor (sign bit = dropped). The
+// dS pass decodes |P| and keep where it consumes p_tr, takes
+// dP = rs·keep∘(dO·Vᵀ), and writes keep ? P : 0 back into the element it just
+// read (each element has one owner lane), so the dV reads after the barrier
+// see P∘keep; dV is scaled by rs at the store.
+template <bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_k(
     const uint16_t *__restrict__ qkv,   // [B, S, 3, H, 64]
     const uint16_t *__restrict__ dctx,  // [B, S, H*64]
     const uint16_t *__restrict__ probs, // [B, H, S, S]
     uint16_t *__restrict__ dqkv,        // [B, S, 3, H, 64]
-    int B, int H, float scale) {
+    int B, int H, float scale, float rs) {
   constexpr int S = 128, D = 64;
   int bh = blockIdx.x;
   int b = bh / H, h = bh % H;
@@ -338,7 +389,7 @@ __global__ __launch_bounds__(256) void attn_bwd_k(
   unsigned pbase = (unsigned)(unsigned long)(
       __attribute__((address_space(3))) const void *)p_tr;
   uint16_t *ds16 = (uint16_t *)ds_tr;
-  const uint16_t *p16 = (const uint16_t *)p_tr;
+  uint16_t *p16 = (uint16_t *)p_tr;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     int sq = sq0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
@@ -348,7 +399,15 @@ __global__ __launch_bounds__(256) void attn_bwd_k(
       int sk = ni * 32 + (lane & 31);
       // element (sq, sk) in the [4 sq][16 sk] subtile image
       int off = ((sq >> 2) * 8 + (sk >> 4)) * 64 + (sq & 3) * 16 + (sk & 15);
-      pv[ni] = bf2f(p16[off]);
+      if (DROP) {
+        uint16_t u = p16[off];
+        bool keep = !(u & 0x8000u); // the bit itself: a dropped +0 is -0
+        pv[ni] = bf2f((uint16_t)(u & 0x7fffu));
+        acc[ni][r] = keep ? acc[ni][r] * rs : 0.f;
+        p16[off] = keep ? u : (uint16_t)0;
+      } else {
+        pv[ni] = bf2f(p16[off]);
+      }
       t += acc[ni][r] * pv[ni];
     }
 #pragma unroll
@@ -441,7 +500,7 @@ __global__ __launch_bounds__(256) void attn_bwd_k(
       for (int ni = 0; ni < 2; ++ni) {
         int d = ni * 32 + (lane & 31);
         dk_out[(long)row * drow + d] = f2bf(dk[ni][r]);
-        dv_out[(long)row * drow + d] = f2bf(dv[ni][r]);
+        dv_out[(long)row * drow + d] = f2bf(DROP ? dv[ni][r] * rs : dv[ni][r]);
       }
     }
   }
@@ -452,9 +511,22 @@ extern "C" hipError_t attn_bwd_launch(const void *qkv, const void *dctx,
                                       int S, int H, float scale,
                                       hipStream_t strm) {
   if (S != 128) return hipErrorInvalidValue; // torch fallback upstream
-  attn_bwd_k<<<B * H, 256, 0, strm>>>(
+  attn_bwd_k<false><<<B * H, 256, 0, strm>>>(
       (const uint16_t *)qkv, (const uint16_t *)dctx, (const uint16_t *)probs,
-      (uint16_t *)dqkv, B, H, scale);
+      (uint16_t *)dqkv, B, H, scale, 1.f);
+  HIP_KERNEL_CHECK();
+  return hipSuccess;
+}
+
+// probs: the sign-coded tensor of attn_drop_fwd_launch; rs = 1/(1 - p_eff)
+extern "C" hipError_t attn_drop_bwd_launch(const void *qkv, const void *dctx,
+                                           const void *probs, void *dqkv,
+                                           float rs, int B, int S, int H,
+                                           float scale, hipStream_t strm) {
+  if (S != 128) return hipErrorInvalidValue; // torch fallback upstream
+  attn_bwd_k<true><<<B * H, 256, 0, strm>>>(
+      (const uint16_t *)qkv, (const uint16_t *)dctx, (const uint16_t *)probs,
+      (uint16_t *)dqkv, B, H, scale, rs);
   HIP_KERNEL_CHECK();
   return hipSuccess;
 }

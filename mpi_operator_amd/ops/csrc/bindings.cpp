@@ -1174,6 +1174,142 @@ static Tensor flash_attn_bwd(const Tensor &qkv, const Tensor &ctx,
   return dqkv;
 }
 
+// ------------- attention with dropout on the probabilities -------------
+// The mask scheme is philox.h's attention scheme (reference.py
+// attn_dropout_keep); state is the device (seed, offset) pair.
+struct AttnDropShape {
+  int B, S, H;
+};
+static AttnDropShape check_attn_drop_qkv(const Tensor &qkv, int64_t heads,
+                                         const char *name) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16, name,
+              " must be a bf16 GPU tensor");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 && qkv.size(4) == 64 &&
+                  qkv.size(0) >= 1 && qkv.size(1) >= 1 && qkv.size(3) >= 1,
+              name, " must be [B,S,3,H,64], got ", qkv.sizes());
+  TORCH_CHECK(qkv.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(heads < 0 || qkv.size(3) == heads, name, " has ", qkv.size(3),
+              " heads, expected ", heads);
+  TORCH_CHECK(attn_dropout_shape_ok(qkv.size(0), qkv.size(3), qkv.size(1)),
+              "attention dropout: B*H*ceil(S/16)*2*S must be below 2^32, got ",
+              qkv.sizes());
+  return {(int)qkv.size(0), (int)qkv.size(1), (int)qkv.size(3)};
+}
+
+static const float *attn_drop_mask(const c10::optional<Tensor> &mask,
+                                   const Tensor &like, long B, long S,
+                                   Tensor &maskc) {
+  if (!mask.has_value()) return nullptr;
+  TORCH_CHECK(mask->is_cuda() && mask->device() == like.device() &&
+                  mask->numel() == B * S,
+              "mask must be an additive [B,S] tensor on qkv's GPU");
+  maskc = mask->to(at::kFloat).contiguous();
+  return maskc.data_ptr<float>();
+}
+
+static void check_attn_ctx(const Tensor &t, const Tensor &qkv,
+                           const AttnDropShape &d, const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == qkv.device() &&
+                  t.scalar_type() == at::kBFloat16 && t.is_contiguous() &&
+                  t.numel() == (long)d.B * d.S * d.H * 64,
+              name, " must be a contiguous bf16 [B,S,H*64] tensor on qkv's GPU");
+}
+
+// returns (ctx [B,S,H*64], signed_probs [B,H,S,S]: bf16(P), sign bit set
+// where dropped)
+static std::vector<Tensor> attn_drop_fwd_b(const Tensor &qkv, int64_t heads,
+                                           double scale,
+                                           const c10::optional<Tensor> &mask,
+                                           const Tensor &state, double p,
+                                           int64_t site) {
+  const AttnDropShape d = check_attn_drop_qkv(qkv, heads, "qkv");
+  TORCH_CHECK(d.S <= 256, "fused attention supports seq <= 256, got ", d.S);
+  check_rng_state(state, qkv);
+  const DropParams dp = check_drop_params(p, site);
+  const HIPDeviceGuard guard(qkv.device());
+  Tensor maskc;
+  const float *mp = attn_drop_mask(mask, qkv, d.B, d.S, maskc);
+  Tensor ctx = at::empty({d.B, d.S, (long)d.H * 64}, qkv.options());
+  Tensor probs = at::empty({d.B, (long)d.H, d.S, d.S}, qkv.options());
+  CHK(attn_drop_fwd_launch(qkv.data_ptr(), ctx.data_ptr(), probs.data_ptr(),
+                           mp, state.data_ptr<int64_t>(), dp.site, dp.thr,
+                           dp.scale, d.B, d.S, d.H, (float)scale,
+                           cur_stream()));
+  return {ctx, probs};
+}
+
+static Tensor attn_drop_bwd_b(const Tensor &qkv, const Tensor &dctx,
+                              const Tensor &signed_probs, double scale,
+                              double p) {
+  const AttnDropShape d = check_attn_drop_qkv(qkv, -1, "qkv");
+  TORCH_CHECK(d.S == 128, "fused attention backward: S must be 128, got ",
+              d.S);
+  check_attn_ctx(dctx, qkv, d, "dctx");
+  TORCH_CHECK(signed_probs.is_cuda() &&
+                  signed_probs.device() == qkv.device() &&
+                  signed_probs.scalar_type() == at::kBFloat16 &&
+                  signed_probs.is_contiguous() &&
+                  signed_probs.numel() == (long)d.B * d.H * d.S * d.S,
+              "signed_probs must be a contiguous bf16 [B,H,S,S] tensor on "
+              "qkv's GPU");
+  const DropParams dp = check_drop_params(p, 0);
+  const HIPDeviceGuard guard(qkv.device());
+  Tensor dqkv = at::empty_like(qkv);
+  CHK(attn_drop_bwd_launch(qkv.data_ptr(), dctx.data_ptr(),
+                           signed_probs.data_ptr(), dqkv.data_ptr(), dp.scale,
+                           d.B, d.S, d.H, (float)scale, cur_stream()));
+  return dqkv;
+}
+
+// returns (ctx [B,S,H*64], lse [B,H,S] fp32 of the UNDROPPED softmax)
+static std::vector<Tensor> flash_attn_drop_fwd_b(
+    const Tensor &qkv, int64_t heads, double scale,
+    const c10::optional<Tensor> &mask, const Tensor &state, double p,
+    int64_t site) {
+  const AttnDropShape d = check_attn_drop_qkv(qkv, heads, "qkv");
+  check_rng_state(state, qkv);
+  const DropParams dp = check_drop_params(p, site);
+  const HIPDeviceGuard guard(qkv.device());
+  Tensor maskc;
+  const float *mp = attn_drop_mask(mask, qkv, d.B, d.S, maskc);
+  Tensor ctx = at::empty({d.B, d.S, (long)d.H * 64}, qkv.options());
+  Tensor lse = at::empty({d.B, (long)d.H, d.S}, qkv.options().dtype(at::kFloat));
+  CHK(flash_attn_drop_fwd_launch(qkv.data_ptr(), ctx.data_ptr(),
+                                 lse.data_ptr<float>(), mp,
+                                 state.data_ptr<int64_t>(), dp.site, dp.thr,
+                                 dp.scale, d.B, d.S, d.H, (float)scale,
+                                 cur_stream()));
+  return {ctx, lse};
+}
+
+// state, p, site: what the forward was given (state unchanged since)
+static Tensor flash_attn_drop_bwd_b(const Tensor &qkv, const Tensor &ctx,
+                                    const Tensor &dctx, const Tensor &lse,
+                                    double scale,
+                                    const c10::optional<Tensor> &mask,
+                                    const Tensor &state, double p,
+                                    int64_t site) {
+  const AttnDropShape d = check_attn_drop_qkv(qkv, -1, "qkv");
+  check_attn_ctx(ctx, qkv, d, "ctx");
+  check_attn_ctx(dctx, qkv, d, "dctx");
+  TORCH_CHECK(lse.is_cuda() && lse.device() == qkv.device() &&
+                  lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.numel() == (long)d.B * d.H * d.S,
+              "lse must be a contiguous fp32 [B,H,S] tensor on qkv's GPU");
+  check_rng_state(state, qkv);
+  const DropParams dp = check_drop_params(p, site);
+  const HIPDeviceGuard guard(qkv.device());
+  Tensor maskc;
+  const float *mp = attn_drop_mask(mask, qkv, d.B, d.S, maskc);
+  Tensor delta = at::empty_like(lse);
+  Tensor dqkv = at::empty_like(qkv);
+  CHK(flash_attn_drop_bwd_launch(
+      qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr<float>(),
+      delta.data_ptr<float>(), mp, state.data_ptr<int64_t>(), dp.site, dp.thr,
+      dp.scale, dqkv.data_ptr(), d.B, d.S, d.H, (float)scale, cur_stream()));
+  return dqkv;
+}
+
 // ------------------------- fused FFN (GELU) -------------------------
 // fc1 forward with the bias+GELU in the epilogue: returns (g, h_pre)
 static std::vector<Tensor> linear_gelu_fwd(const Tensor &x, const Tensor &w,
@@ -1717,6 +1853,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("flash_attn_fwd", &flash_attn_fwd);
   m.def("flash_attn_bwd", &flash_attn_bwd);
+  m.def("attn_drop_fwd", &attn_drop_fwd_b, py::arg("qkv"), py::arg("heads"),
+        py::arg("scale"), py::arg("mask"), py::arg("state"), py::arg("p"),
+        py::arg("site"));
+  m.def("attn_drop_bwd", &attn_drop_bwd_b, py::arg("qkv"), py::arg("dctx"),
+        py::arg("signed_probs"), py::arg("scale"), py::arg("p"));
+  m.def("flash_attn_drop_fwd", &flash_attn_drop_fwd_b, py::arg("qkv"),
+        py::arg("heads"), py::arg("scale"), py::arg("mask"), py::arg("state"),
+        py::arg("p"), py::arg("site"));
+  m.def("flash_attn_drop_bwd", &flash_attn_drop_bwd_b, py::arg("qkv"),
+        py::arg("ctx"), py::arg("dctx"), py::arg("lse"), py::arg("scale"),
+        py::arg("mask"), py::arg("state"), py::arg("p"), py::arg("site"));
   m.def("linear_wgrad_only", &linear_wgrad_only);
   m.def("linear_gelu_dgrad", &linear_gelu_dgrad);
   m.def("masked_xent_bwd", &masked_xent_bwd);

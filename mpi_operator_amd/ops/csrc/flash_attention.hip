@@ -26,8 +26,18 @@
 //
 // Layouts: qkv / dqkv [B, S, 3, H, 64]; ctx / dctx [B, S, H·64];
 // lse / delta [B, H, S] fp32; mask [B, S] fp32 additive (or nullptr).
+//
+// DROP (template parameter of the three MFMA kernels): dropout on P with the
+// attention mask scheme of philox.h, keep drawn in the kernels and never
+// stored — the backward regenerates it from (state, site, position):
+//   O  = rs·(P∘keep)·V          rs = 1/(1 − p_eff), applied in fp32
+//   dV = rs·(P∘keep)ᵀ·dO
+//   dS = (rs·keep∘dP − delta)∘P·scale
+// m, l and lse are those of the undropped softmax, and delta = rowsum(dO∘O)
+// still equals rowsum(dP_eff∘P), so the delta kernel is shared.
 #include "common.h"
 #include "launchers.h"
+#include "philox.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8a;
 typedef __attribute__((ext_vector_type(16))) float float16a;
@@ -139,12 +149,13 @@ DEV_INLINE float16a fa_nt_frag(const bf16x8a af[4], const ushort8 *img, int ni,
 // ------------------------------ forward ------------------------------
 // grid (B·H, ceil(S/128)); LDS K 16 KiB + V 16 KiB + P 32 KiB = 64 KiB
 // (2 workgroups per CU).
+template <bool DROP>
 __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
     const uint16_t *__restrict__ qkv, // [B, S, 3, H, 64]
     uint16_t *__restrict__ ctx,       // [B, S, H*64]
     float *__restrict__ lse,          // [B, H, S]
     const float *__restrict__ mask,   // [B, S] additive (or nullptr)
-    int B, int S, int H, float scale) {
+    int B, int S, int H, float scale, AttnDropArgs da) {
   constexpr int D = FA_D, T = FA_T;
   int bh = blockIdx.x;
   int b = bh / H, h = bh % H;
@@ -173,6 +184,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
     l_run[r] = 0.f;
   }
   float16a oacc[2] = {};
+  AttnDrop dr{};
+  if (DROP) dr = attn_drop_init(da, bh, S);
 
   const int nkt = (S + T - 1) / T;
   for (int kt = 0; kt < nkt; ++kt) {
@@ -234,13 +247,30 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
       oacc[1][r] *= alpha;
     }
 
-    // park the (unnormalized) P tile in this wave's LDS image
+    // park the (unnormalized) P tile in this wave's LDS image; DROP parks
+    // e·keep (m and l above are the undropped ones). The keep bits are
+    // drawn one column fragment at a time, by every lane alike (columns
+    // >= S hold e = 0 whatever they draw), and selected, never branched on.
+    if constexpr (DROP) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int prow = fa_crow(r, lane);
+      for (int ni = 0; ni < 4; ++ni) {
+        uint32_t kb = attn_drop_keep16(dr, (uint32_t)qrow0 >> 4, lane >> 5,
+                                       k0 + ni * 32 + (lane & 31));
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        p_img[wave][prow][ni * 32 + (lane & 31)] = f2bf(acc[ni][r]);
+        for (int r = 0; r < 16; ++r) {
+          uint16_t pv = f2bf(acc[ni][r]);
+          p_img[wave][fa_crow(r, lane)][ni * 32 + (lane & 31)] =
+              ((kb >> r) & 1u) ? pv : (uint16_t)0;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int prow = fa_crow(r, lane);
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+          p_img[wave][prow][ni * 32 + (lane & 31)] = f2bf(acc[ni][r]);
+      }
     }
     // per-wave private image: a wave-level LDS fence suffices
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -270,7 +300,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
     int row = qrow0 + fa_crow(r, lane);
     if (row >= S) continue;
     float l = l_run[r];
-    float inv = l > 0.f ? 1.f / l : 0.f;
+    float inv = l > 0.f ? (DROP ? da.rs / l : 1.f / l) : 0.f;
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
       cp[(long)row * crow + ni * 32 + (lane & 31)] = f2bf(oacc[ni][r] * inv);
@@ -284,8 +314,21 @@ extern "C" hipError_t flash_attn_fwd_launch(const void *qkv, void *ctx,
                                             int B, int S, int H, float scale,
                                             hipStream_t strm) {
   if (S < 1) return hipErrorInvalidValue;
-  flash_attn_fwd_k<<<dim3(B * H, (S + FA_T - 1) / FA_T), 256, 0, strm>>>(
-      (const uint16_t *)qkv, (uint16_t *)ctx, lse, mask, B, S, H, scale);
+  flash_attn_fwd_k<false><<<dim3(B * H, (S + FA_T - 1) / FA_T), 256, 0, strm>>>(
+      (const uint16_t *)qkv, (uint16_t *)ctx, lse, mask, B, S, H, scale,
+      AttnDropArgs{});
+  HIP_KERNEL_CHECK();
+  return hipSuccess;
+}
+
+extern "C" hipError_t flash_attn_drop_fwd_launch(
+    const void *qkv, void *ctx, float *lse, const float *mask,
+    const int64_t *state, uint32_t site, uint32_t thr, float rs, int B, int S,
+    int H, float scale, hipStream_t strm) {
+  if (S < 1 || !state) return hipErrorInvalidValue;
+  flash_attn_fwd_k<true><<<dim3(B * H, (S + FA_T - 1) / FA_T), 256, 0, strm>>>(
+      (const uint16_t *)qkv, (uint16_t *)ctx, lse, mask, B, S, H, scale,
+      AttnDropArgs{state, site, thr, rs});
   HIP_KERNEL_CHECK();
   return hipSuccess;
 }
@@ -321,22 +364,35 @@ __global__ __launch_bounds__(256) void flash_attn_delta_k(
 // P and dS fragment (32 q-rows × 32 keys) recomputed from lse/delta and
 // written as bf16 into [4 q][16 key] subtile images. `p16` may be nullptr
 // (the dQ kernel needs dS only). Rows/keys >= S get exactly 0.
+// DROP: the forward's keep bits are drawn again (band0 = global row of the
+// wave's first q-row >> 4, gcol = this lane's global key column): the p16
+// image takes p·keep and dS = (dp·keep·rs − delta)·p·scale.
+template <bool DROP>
 DEV_INLINE void fa_pds_frag(const bf16x8a qf[4], const bf16x8a dof[4],
                             const ushort8 *k_nt, const ushort8 *v_nt, int ni,
                             int lane, int sqw, bool cok, float mk,
                             const float lse_r[16], const float delta_r[16],
                             const bool rok[16], float scale, uint16_t *p16,
-                            uint16_t *ds16) {
+                            uint16_t *ds16, const AttnDrop &dr, uint32_t band0,
+                            uint32_t gcol) {
   float16a s = fa_nt_frag(qf, k_nt, ni, lane);
   float16a dp = fa_nt_frag(dof, v_nt, ni, lane);
   int col = ni * 32 + (lane & 31);
+  uint32_t kb = 0;
+  if (DROP) kb = attn_drop_keep16(dr, band0, lane >> 5, gcol);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     int row = sqw + fa_crow(r, lane);
     float p = (cok && rok[r]) ? __expf(s[r] * scale + mk - lse_r[r]) : 0.f;
-    float ds = (dp[r] - delta_r[r]) * p * scale;
+    float dpe = dp[r], pk = p;
+    if (DROP) {
+      bool keep = (kb >> r) & 1u;
+      dpe = keep ? dp[r] * dr.rs : 0.f;
+      pk = keep ? p : 0.f;
+    }
+    float ds = (dpe - delta_r[r]) * p * scale;
     int off = fa_sub128(row, col);
-    if (p16) p16[off] = f2bf(p);
+    if (p16) p16[off] = f2bf(pk);
     ds16[off] = f2bf(ds);
   }
 }
@@ -344,6 +400,7 @@ DEV_INLINE void fa_pds_frag(const bf16x8a qf[4], const bf16x8a dof[4],
 // dK, dV: grid (B·H, ceil(S/128)) over key chunks, loop over q-chunks.
 // LDS: K, V (NT, staged once) + Q, dO (subtile, per q-chunk) 4×16 KiB
 // + P, dS 2×32 KiB = 128 KiB.
+template <bool DROP>
 __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
     const uint16_t *__restrict__ qkv,   // [B, S, 3, H, 64]
     const uint16_t *__restrict__ dctx,  // [B, S, H*64]
@@ -351,7 +408,7 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
     const float *__restrict__ delta,    // [B, H, S]
     const float *__restrict__ mask,     // [B, S] or nullptr
     uint16_t *__restrict__ dqkv,        // [B, S, 3, H, 64]
-    int B, int S, int H, float scale) {
+    int B, int S, int H, float scale, AttnDropArgs da) {
   constexpr int D = FA_D, T = FA_T;
   int bh = blockIdx.x;
   int b = bh / H, h = bh % H;
@@ -389,6 +446,8 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
 
   const int sqw = wave * 32; // recompute: q-rows; accumulate: key rows
   float16a dk[2] = {}, dv[2] = {};
+  AttnDrop dr{};
+  if (DROP) dr = attn_drop_init(da, bh, S);
   const int nqc = (S + T - 1) / T;
   for (int qc = 0; qc < nqc; ++qc) {
     const int q0 = qc * T;
@@ -413,8 +472,10 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
     }
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni)
-      fa_pds_frag(qf, dof, k_nt, v_nt, ni, lane, sqw, cok[ni], mk[ni], lse_r,
-                  delta_r, rok, scale, (uint16_t *)p_tr, (uint16_t *)ds_tr);
+      fa_pds_frag<DROP>(qf, dof, k_nt, v_nt, ni, lane, sqw, cok[ni], mk[ni],
+                        lse_r, delta_r, rok, scale, (uint16_t *)p_tr,
+                        (uint16_t *)ds_tr, dr, (uint32_t)(q0 + sqw) >> 4,
+                        kc0 + ni * 32 + (lane & 31));
     __syncthreads();
 
     // dK += dSᵀ·Q, dV += Pᵀ·dO: rows = this wave's 32 keys, k = the 128 q
@@ -444,7 +505,7 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
     for (int ni = 0; ni < 2; ++ni) {
       int d = ni * 32 + (lane & 31);
       dk_out[(long)row * qrow + d] = f2bf(dk[ni][r]);
-      dv_out[(long)row * qrow + d] = f2bf(dv[ni][r]);
+      dv_out[(long)row * qrow + d] = f2bf(DROP ? dv[ni][r] * da.rs : dv[ni][r]);
     }
   }
 }
@@ -453,11 +514,12 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
 // LDS: K, V (NT) + K (subtile) 3×16 KiB + dS 32 KiB = 80 KiB. The dS image
 // is written and read by the same wave (its own 32 q-rows = 8 private row
 // blocks), so it needs a wave-level fence only.
+template <bool DROP>
 __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
     const uint16_t *__restrict__ qkv, const uint16_t *__restrict__ dctx,
     const float *__restrict__ lse, const float *__restrict__ delta,
     const float *__restrict__ mask, uint16_t *__restrict__ dqkv, int B, int S,
-    int H, float scale) {
+    int H, float scale, AttnDropArgs da) {
   constexpr int D = FA_D, T = FA_T;
   int bh = blockIdx.x;
   int b = bh / H, h = bh % H;
@@ -493,6 +555,8 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
   }
 
   float16a dq[2] = {};
+  AttnDrop dr{};
+  if (DROP) dr = attn_drop_init(da, bh, S);
   const int nkt = (S + T - 1) / T;
   for (int kt = 0; kt < nkt; ++kt) {
     const int k0 = kt * T;
@@ -507,8 +571,9 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
       int col = k0 + ni * 32 + (lane & 31);
       bool cok = col < S;
       float mk = (mask && cok) ? mask[(long)b * S + col] : 0.f;
-      fa_pds_frag(qf, dof, k_nt, v_nt, ni, lane, sqw, cok, mk, lse_r, delta_r,
-                  rok, scale, nullptr, (uint16_t *)ds_tr);
+      fa_pds_frag<DROP>(qf, dof, k_nt, v_nt, ni, lane, sqw, cok, mk, lse_r,
+                        delta_r, rok, scale, nullptr, (uint16_t *)ds_tr, dr,
+                        (uint32_t)(q0 + sqw) >> 4, col);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
@@ -549,13 +614,37 @@ extern "C" hipError_t flash_attn_bwd_launch(
       (const uint16_t *)ctx, (const uint16_t *)dctx, delta, B, S, H);
   HIP_KERNEL_CHECK();
   dim3 grid(B * H, (S + FA_T - 1) / FA_T);
-  flash_attn_bwd_dkv_k<<<grid, 256, 0, strm>>>(
+  flash_attn_bwd_dkv_k<false><<<grid, 256, 0, strm>>>(
       (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale);
+      (uint16_t *)dqkv, B, S, H, scale, AttnDropArgs{});
   HIP_KERNEL_CHECK();
-  flash_attn_bwd_dq_k<<<grid, 256, 0, strm>>>(
+  flash_attn_bwd_dq_k<false><<<grid, 256, 0, strm>>>(
       (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale);
+      (uint16_t *)dqkv, B, S, H, scale, AttnDropArgs{});
+  HIP_KERNEL_CHECK();
+  return hipSuccess;
+}
+
+// state, site, thr, rs: those of the forward; the masks are drawn again
+extern "C" hipError_t flash_attn_drop_bwd_launch(
+    const void *qkv, const void *ctx, const void *dctx, const float *lse,
+    float *delta, const float *mask, const int64_t *state, uint32_t site,
+    uint32_t thr, float rs, void *dqkv, int B, int S, int H, float scale,
+    hipStream_t strm) {
+  if (S < 1 || !state) return hipErrorInvalidValue;
+  long nthr = (long)B * S * H * 8;
+  flash_attn_delta_k<<<cdiv_h(nthr, 256), 256, 0, strm>>>(
+      (const uint16_t *)ctx, (const uint16_t *)dctx, delta, B, S, H);
+  HIP_KERNEL_CHECK();
+  dim3 grid(B * H, (S + FA_T - 1) / FA_T);
+  AttnDropArgs da{state, site, thr, rs};
+  flash_attn_bwd_dkv_k<true><<<grid, 256, 0, strm>>>(
+      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
+      (uint16_t *)dqkv, B, S, H, scale, da);
+  HIP_KERNEL_CHECK();
+  flash_attn_bwd_dq_k<true><<<grid, 256, 0, strm>>>(
+      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
+      (uint16_t *)dqkv, B, S, H, scale, da);
   HIP_KERNEL_CHECK();
   return hipSuccess;
 }

@@ -145,6 +145,16 @@ hipError_t attn_fwd_launch(const void *qkv, void *ctx, void *probs,
 hipError_t attn_bwd_launch(const void *qkv, const void *dctx,
                            const void *probs, void *dqkv, int B, int S, int H,
                            float scale, hipStream_t strm);
+// dropout on P (philox.h attention scheme): state is the device (seed,
+// offset) pair, thr and rs from dropout_thr_scale(p); probs carries bf16(P)
+// with the sign bit set where dropped and is all the backward needs
+hipError_t attn_drop_fwd_launch(const void *qkv, void *ctx, void *probs,
+                                const float *mask, const int64_t *state,
+                                uint32_t site, uint32_t thr, float rs, int B,
+                                int S, int H, float scale, hipStream_t strm);
+hipError_t attn_drop_bwd_launch(const void *qkv, const void *dctx,
+                                const void *probs, void *dqkv, float rs, int B,
+                                int S, int H, float scale, hipStream_t strm);
 
 // ---- flash_attention.hip ----
 hipError_t flash_attn_fwd_launch(const void *qkv, void *ctx, float *lse,
@@ -155,6 +165,20 @@ hipError_t flash_attn_bwd_launch(const void *qkv, const void *ctx,
                                  float *delta, const float *mask, void *dqkv,
                                  int B, int S, int H, float scale,
                                  hipStream_t strm);
+// the same with dropout on P; the backward draws the forward's masks again
+// from the same (state, site), so state must hold what the forward read
+hipError_t flash_attn_drop_fwd_launch(const void *qkv, void *ctx, float *lse,
+                                      const float *mask, const int64_t *state,
+                                      uint32_t site, uint32_t thr, float rs,
+                                      int B, int S, int H, float scale,
+                                      hipStream_t strm);
+hipError_t flash_attn_drop_bwd_launch(const void *qkv, const void *ctx,
+                                      const void *dctx, const float *lse,
+                                      float *delta, const float *mask,
+                                      const int64_t *state, uint32_t site,
+                                      uint32_t thr, float rs, void *dqkv,
+                                      int B, int S, int H, float scale,
+                                      hipStream_t strm);
 
 // ---- gemm.hip ----
 hipError_t gemm_nt(const void *a, const void *b, void *c, int M, int N, int K,

@@ -66,6 +66,59 @@ DEV_INLINE uint32_t drop_keep8(const DropState &st, uint32_t site,
   return bits;
 }
 
+// ---- attention-probability dropout (attention.hip, flash_attention.hip) ----
+// The mask of P[bh, i, j] (bh = b·H + h, query row i, key column j), in
+// layout-free terms; ops/reference.py attn_dropout_keep mirrors it:
+//
+//   u = i & 15, band = i >> 4, half = (u >> 2) & 1,
+//   slot = (u & 3) + 4·(u >> 3), NB = ceil(S / 16)
+//   call = ((bh·NB + band)·2 + half)·S + j          counter word 0
+//   counter = (call, site, offset_lo, offset_hi), key = (seed_lo, seed_hi)
+//   r = (w[slot >> 1] >> 16·(slot & 1)) & 0xffff,  kept iff r >= thr
+//
+// One call serves the 8 rows {4·half + (s & 3) + 8·(s >> 2)} of one 16-row
+// band at one column: exactly what one lane holds of a 32×32 MFMA result
+// (row (r&3) + 8·(r>>2) + 4·(lane>>5) of the wave's 32, column lane&31) in
+// registers r = 8k..8k+7, k the band within the wave's rows, with slot =
+// r & 7 and half = lane >> 5. No draw is wasted and no lane exchanges bits.
+struct AttnDrop {
+  DropState st;
+  uint32_t site, thr;
+  float rs;      // 1 / (1 - p_eff)
+  uint32_t bhnb; // bh·NB
+  uint32_t S;
+};
+
+// launch arguments of the DROP kernels (unused where DROP is false)
+struct AttnDropArgs {
+  const int64_t *state;
+  uint32_t site, thr;
+  float rs;
+};
+
+DEV_INLINE AttnDrop attn_drop_init(const AttnDropArgs &a, int bh, int S) {
+  uint32_t nb = (uint32_t)(S + 15) >> 4;
+  return {drop_state(a.state), a.site, a.thr, a.rs, (uint32_t)bh * nb,
+          (uint32_t)S};
+}
+
+// keep bits of the 16 C-layout registers of one lane at key column j: bit r
+// set = register r survives. band0 = (first of the wave's 32 rows) >> 4.
+DEV_INLINE uint32_t attn_drop_keep16(const AttnDrop &d, uint32_t band0,
+                                     uint32_t half, uint32_t j) {
+  uint32_t c0 = ((d.bhnb + band0) * 2 + half) * d.S + j;
+  uint32_t c1 = c0 + 2 * d.S; // band0 + 1
+  return drop_keep8(d.st, d.site, d.thr, c0) |
+         (drop_keep8(d.st, d.site, d.thr, c1) << 8);
+}
+
+// 32-bit call counter: B·H·NB·2·S calls
+static inline bool attn_dropout_shape_ok(long B, long H, long S) {
+  if (B < 1 || H < 1 || S < 1) return false;
+  long nb = (S + 15) / 16;
+  return B * H * nb * 2 * S < (1L << 32);
+}
+
 // Host side: p -> (thr, scale). False when p is outside [0, 1) or rounds to
 // thr = 65536 (everything dropped, scale infinite). nearbyint rounds half to
 // even, as Python's round() does in the reference.

@@ -494,8 +494,66 @@ class AttentionFn(torch.autograd.Function):
         return dqkv, None, None, None
 
 
-def attention(qkv, heads, scale, mask=None):
-    return AttentionFn.apply(qkv, heads, scale, mask)
+class AttentionDropFn(torch.autograd.Function):
+    """AttentionFn with dropout on the probabilities, drawn inside the
+    kernel (csrc/philox.h attention scheme). The saved probs tensor is
+    bf16(P) with the sign bit set where dropped — P >= 0, so it carries the
+    mask at no extra memory and the backward draws nothing."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, scale, mask, p, state, site):
+        qkv = qkv.contiguous()
+        out, probs = hip_ext().attn_drop_fwd(qkv, heads, scale, mask, state,
+                                             p, site)
+        ctx.save_for_backward(qkv, probs)
+        ctx.scale, ctx.p = scale, p
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, probs = ctx.saved_tensors
+        B, S, _, H, D = qkv.shape
+        none = (None,) * 6
+        if S == 128 and D == 64:
+            return (hip_ext().attn_drop_bwd(qkv, dout.contiguous(), probs,
+                                            ctx.scale, ctx.p),) + none
+        rs = ref.dropout_threshold(ctx.p)[2]
+        q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))  # B,H,S,D
+        do = dout.view(B, S, H, D).transpose(1, 2)
+        # the sign bit itself, not `< 0`: a dropped +0 is -0
+        keep = ~torch.signbit(probs)
+        p = probs.abs().float()
+        pk = torch.where(keep, probs, torch.zeros((), dtype=probs.dtype,
+                                                  device=probs.device))
+        dv = (torch.matmul(pk.transpose(-1, -2), do).float() * rs).to(do.dtype)
+        dp = torch.matmul(do, v.transpose(-1, -2)).float() * keep * rs
+        ds = (dp - (dp * p).sum(-1, keepdim=True)) * p * ctx.scale
+        ds = ds.to(do.dtype)
+        dq = torch.matmul(ds, k)
+        dk = torch.matmul(ds.transpose(-1, -2), q)
+        dqkv = torch.stack(
+            [dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2)],
+            dim=2)
+        return (dqkv,) + none
+
+
+def _check_attn_dropout(qkv, p, rng):
+    _check_p(p)
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16):
+        raise ValueError("attention dropout (p > 0) runs on GPU bf16 only")
+    if rng is None:
+        raise ValueError("attention dropout (p > 0) needs a DropoutRng")
+
+
+def attention(qkv, heads, scale, mask=None, p: float = 0.0, rng=None,
+              site: int = 0):
+    """Fused MHA for S <= 256. p > 0 (GPU bf16 only) drops out the softmax
+    output with masks from `rng` at call site `site`; p == 0 is the
+    dropout-free kernel itself."""
+    if p == 0:
+        return AttentionFn.apply(qkv, heads, scale, mask)
+    _check_attn_dropout(qkv, p, rng)
+    return AttentionDropFn.apply(qkv, heads, scale, mask, p, rng.state, site)
 
 
 class FlashAttentionFn(torch.autograd.Function):
@@ -528,15 +586,48 @@ class FlashAttentionFn(torch.autograd.Function):
         return dqkv, None, None, None
 
 
-def flash_attention(qkv, heads, scale, mask=None):
+class FlashAttentionDropFn(torch.autograd.Function):
+    """FlashAttentionFn with dropout on the probabilities. Nothing of the
+    mask is saved: the backward kernels draw it again from the random-number
+    state the forward read. That state is cloned in forward (16 bytes, a
+    device copy: capturable), so an rng.tick() between forward and backward
+    cannot desynchronise the two."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, scale, mask, p, state, site):
+        qkv = qkv.contiguous()
+        state = state.clone()
+        out, lse = hip_ext().flash_attn_drop_fwd(qkv, heads, scale, mask,
+                                                 state, p, site)
+        ctx.save_for_backward(qkv, out, lse, mask, state)
+        ctx.scale, ctx.p, ctx.site = scale, p, site
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, mask, state = ctx.saved_tensors
+        dqkv = hip_ext().flash_attn_drop_bwd(qkv, out, dout.contiguous(), lse,
+                                             ctx.scale, mask, state, ctx.p,
+                                             ctx.site)
+        return (dqkv,) + (None,) * 6
+
+
+def flash_attention(qkv, heads, scale, mask=None, p: float = 0.0, rng=None,
+                    site: int = 0):
     """softmax(Q·Kᵀ·scale + mask)·V for qkv [B, S, 3, H, 64] → [B, S, H·64].
 
     mask: optional additive key mask [B, S] (0 = keep, a large negative
     such as finfo(float32).min = drop), shared by all heads and query rows.
     CUDA bf16 runs the HIP kernels; anything else the fp32 reference.
     A batch row with NO valid key is outside the contract: its output and
-    gradients are only guaranteed to be finite."""
-    return FlashAttentionFn.apply(qkv, heads, scale, mask)
+    gradients are only guaranteed to be finite.
+    p > 0 (GPU bf16 only) drops out the softmax output with masks from
+    `rng` at call site `site`; p == 0 is the dropout-free path itself."""
+    if p == 0:
+        return FlashAttentionFn.apply(qkv, heads, scale, mask)
+    _check_attn_dropout(qkv, p, rng)
+    return FlashAttentionDropFn.apply(qkv, heads, scale, mask, p, rng.state,
+                                      site)
 
 
 class BertLayerFn(torch.autograd.Function):

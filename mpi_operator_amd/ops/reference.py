@@ -238,23 +238,33 @@ def _flash_scores(qkv, scale: float, mask):
     return s, q, k, v
 
 
-def flash_attention_fwd(qkv, heads: int, scale: float, mask=None):
+def flash_attention_fwd(qkv, heads: int, scale: float, mask=None, keep=None,
+                        drop_scale: float = 1.0):
     """Specification of flash_attn_fwd_k. qkv [B,S,3,H,D], mask [B,S]
     additive or None → (ctx [B,S,H·D] in qkv's dtype, lse [B,H,S] fp32).
-    Keeps the per-row log-sum-exp, not the probabilities."""
+    Keeps the per-row log-sum-exp, not the probabilities.
+    keep (bool [B,H,S,S]) and drop_scale = 1/(1 - p_eff) apply dropout to
+    the probabilities: ctx = drop_scale·(P∘keep)·V; lse is that of the
+    undropped softmax."""
     B, S, _, H, D = qkv.shape
     assert H == heads
     s, _, _, v = _flash_scores(qkv, scale, mask)
     lse = torch.logsumexp(s, dim=-1)
     p = torch.exp(s - lse.unsqueeze(-1))
+    if keep is not None:
+        p = p * keep.to(p.dtype) * drop_scale
     ctx = torch.matmul(p, v).transpose(1, 2).reshape(B, S, H * D)
     return ctx.to(qkv.dtype), lse
 
 
-def flash_attention_bwd(qkv, ctx, dctx, lse, scale: float, mask=None):
+def flash_attention_bwd(qkv, ctx, dctx, lse, scale: float, mask=None,
+                        keep=None, drop_scale: float = 1.0):
     """Specification of the flash backward kernels: P is recomputed from
     lse and the softmax-gradient row term is delta = rowsum(dctx∘ctx);
-    no saved probabilities. Returns dqkv [B,S,3,H,D]."""
+    no saved probabilities. Returns dqkv [B,S,3,H,D].
+    With keep / drop_scale (see flash_attention_fwd): dP = drop_scale·keep∘
+    (dO·Vᵀ), dV = drop_scale·(P∘keep)ᵀ·dO, and delta is unchanged, since
+    rowsum(dP∘P) = rowsum(dO∘O) still holds for the dropped O."""
     B, S, _, H, D = qkv.shape
     s, q, k, v = _flash_scores(qkv, scale, mask)
     p = torch.exp(s - lse.float().unsqueeze(-1))
@@ -262,8 +272,13 @@ def flash_attention_bwd(qkv, ctx, dctx, lse, scale: float, mask=None):
     o = ctx.reshape(B, S, H, D).transpose(1, 2).float()
     delta = (do * o).sum(-1, keepdim=True)
     dp = torch.matmul(do, v.transpose(-1, -2))
+    pk = p
+    if keep is not None:
+        kf = keep.to(p.dtype) * drop_scale
+        dp = dp * kf
+        pk = p * kf
     ds = (dp - delta) * p * scale
-    dv = torch.matmul(p.transpose(-1, -2), do)
+    dv = torch.matmul(pk.transpose(-1, -2), do)
     dq = torch.matmul(ds, k)
     dk = torch.matmul(ds.transpose(-1, -2), q)
     dqkv = torch.stack(
@@ -338,3 +353,52 @@ def philox_dropout_mask(seed: int, offset: int, site: int, shape, p: float):
         r[:, j] = (w[j >> 1] >> np.uint32(16 * (j & 1))) & np.uint32(0xFFFF)
     keep = r >= np.uint32(thr)
     return torch.from_numpy(keep.reshape(tuple(int(d) for d in shape)))
+
+
+def attn_dropout_call_slot(B: int, H: int, S: int):
+    """(call, slot), int64 [B·H, S, S] each: the Philox call (counter word 0)
+    and the 16-bit slot 0..7 within it that element (bh, i, j) of the
+    attention probabilities draws from — csrc/philox.h's attention scheme:
+    u = i & 15, band = i >> 4, half = (u >> 2) & 1,
+    slot = (u & 3) + 4·(u >> 3), NB = ceil(S/16),
+    call = ((bh·NB + band)·2 + half)·S + j."""
+    import numpy as np
+    nb = (S + 15) // 16
+    if B < 1 or H < 1 or S < 1 or B * H * nb * 2 * S >= 1 << 32:
+        raise ValueError(f"B·H·ceil(S/16)·2·S must be in [1, 2^32), got "
+                         f"B={B} H={H} S={S}")
+    bh = np.arange(B * H, dtype=np.int64)[:, None, None]
+    i = np.arange(S, dtype=np.int64)[None, :, None]
+    j = np.arange(S, dtype=np.int64)[None, None, :]
+    u = i & 15
+    band, half = i >> 4, (u >> 2) & 1
+    slot = (u & 3) + 4 * (u >> 3)
+    call = ((bh * nb + band) * 2 + half) * S + j
+    return call, np.broadcast_to(slot, call.shape)
+
+
+def attn_dropout_keep(seed: int, offset: int, site: int, B: int, H: int,
+                      S: int, p: float):
+    """The keep mask (True = kept), bool [B,H,S,S], that the attention
+    kernels draw for the softmax output of a [B,S,3,H,64] qkv: key (seed_lo,
+    seed_hi), counter (call, site, offset_lo, offset_hi) with call and slot of
+    attn_dropout_call_slot; r = (w[slot >> 1] >> 16·(slot & 1)) & 0xffff,
+    kept iff r >= thr."""
+    import numpy as np
+    thr, _, _ = dropout_threshold(p)
+    if not 0 <= site < 1 << 32:
+        raise ValueError(f"site {site} does not fit a uint32")
+    seed &= (1 << 64) - 1
+    offset &= (1 << 64) - 1
+    call, slot = attn_dropout_call_slot(B, H, S)
+    # one evaluation per distinct call: [B·H·NB·2·S]
+    nb = (S + 15) // 16
+    w = philox4x32_10(
+        (np.arange(B * H * nb * 2 * S, dtype=np.uint64), site,
+         offset & 0xFFFFFFFF, offset >> 32),
+        (seed & 0xFFFFFFFF, seed >> 32))
+    w = np.stack(w, axis=-1)  # [calls, 4]
+    word = w[call, slot >> 1]
+    r = (word >> (16 * (slot & 1)).astype(np.uint32)) & np.uint32(0xFFFF)
+    keep = r >= np.uint32(thr)
+    return torch.from_numpy(np.ascontiguousarray(keep.reshape(B, H, S, S)))

@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--graph", type=int, default=1)
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lamb"])
     ap.add_argument("--dropout", type=float, default=0.0)
+    ap.add_argument("--attn-dropout", type=float, default=0.0,
+                    help="dropout on the attention probabilities")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
 
@@ -34,7 +36,8 @@ def main():
     from mpi_operator_amd.optim import FusedAdamW, FusedLAMB, FusedSGD
 
     torch.manual_seed(0)
-    m = B.to_mi355x_bert(getattr(B, args.model)(args.dropout), "cuda")
+    m = B.to_mi355x_bert(
+        getattr(B, args.model)(args.dropout, args.attn_dropout), "cuda")
     m.train()
     m.seed_dropout(args.seed + hvd.rank())
     if args.optimizer == "sgd":
