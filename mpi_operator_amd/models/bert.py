@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -130,15 +131,57 @@ class SelfAttention(nn.Module):
         self.out = BertLinear(cfg.hidden, cfg.hidden)
         self.scale = 1.0 / math.sqrt(self.head_dim)
 
-    def forward(self, x, attn_mask=None, p=0.0, rng=None, site=0):
+    def _packed(self, qkv, cu_seqlens, max_seqlen, hip, p, rng, site):
+        """Attention over a packed batch: qkv [1, T, 3, nh, hd], sequence n
+        in rows cu_seqlens[n]..cu_seqlens[n+1]−1 → ctx [1, T, h], zeros at
+        or past cu_seqlens[-1]."""
+        _, t, _, nh, hd = qkv.shape
+        if hip:
+            # no host read of cu_seqlens: graph-safe
+            ctx = Fx.flash_attention_varlen(
+                qkv.view(t, 3, nh, hd), cu_seqlens, max_seqlen, nh, self.scale,
+                p, rng, site)
+            return ctx.view(1, t, nh * hd)
+        # eager per-sequence chain (reads cu_seqlens on the host)
+        cu = [int(c) for c in cu_seqlens.tolist()]
+        parts = []
+        for a, e in zip(cu, cu[1:]):
+            if e == a:
+                continue
+            q, k, v = (qkv[0, a:e, i].transpose(0, 1) for i in range(3))
+            scores = torch.matmul(q, k.transpose(-1, -2)) * self.scale
+            probs = torch.softmax(scores.float(), dim=-1).to(v.dtype)
+            if p > 0:
+                probs = F.dropout(probs, p, training=True)
+            parts.append(torch.matmul(probs, v).transpose(0, 1)
+                         .reshape(e - a, nh * hd))
+        if cu[-1] < t:
+            parts.append(qkv.new_zeros(t - cu[-1], nh * hd))
+        return torch.cat(parts, dim=0)[None]
+
+    def forward(self, x, attn_mask=None, p=0.0, rng=None, site=0, *,
+                cu_seqlens=None, max_seqlen=None):
         """p, rng, site: dropout on the attention probabilities (p = 0
         outside training). The HIP kernels draw it themselves from `rng` at
         `site`; without an rng (CPU, other dtypes) the eager chain applies
-        F.dropout to probs."""
+        F.dropout to probs.
+        cu_seqlens (int32 [N + 1]), max_seqlen: x is a packed batch
+        [1, T, hidden] of N sequences that attend to themselves only (see
+        Fx.flash_attention_varlen); there is no attn_mask then."""
         b, s, h = x.shape
         qkv = self.qkv(x).view(b, s, 3, self.heads, self.head_dim)
         hip = (x.is_cuda and x.dtype == torch.bfloat16 and self.head_dim == 64
                and (p == 0 or rng is not None))
+        if cu_seqlens is not None:
+            if attn_mask is not None:
+                raise ValueError("a packed batch (cu_seqlens) has no pad "
+                                 "keys: attn_mask must be None")
+            if b != 1:
+                raise ValueError(f"a packed batch is [1, T, hidden], got "
+                                 f"{tuple(x.shape)}")
+            return self.out(self._packed(
+                qkv, cu_seqlens, s if max_seqlen is None else max_seqlen, hip,
+                p, rng, site))
         if hip and s <= 256 and attn_mask is None:
             # fused QKᵀ→softmax→PV kernel (one launch per step instead of
             # the batched-matmul + softmax chain); emits ctx in [b, s, h]
@@ -192,12 +235,15 @@ class BertLayer(nn.Module):
         return ln(a + b)
 
     def forward(self, x, attn_mask=None, p=0.0, rng=None, site=0,
-                attn_p=0.0, attn_site=0):
+                attn_p=0.0, attn_site=0, *, cu_seqlens=None, max_seqlen=None):
         """p, rng, site: BertModel's hidden-state dropout for this call
         (p = 0 outside training); the attention-output join draws at `site`,
         the FFN-output join at `site + 1`. attn_p, attn_site: dropout on the
-        attention probabilities, drawn from the same rng at `attn_site`."""
+        attention probabilities, drawn from the same rng at `attn_site`.
+        cu_seqlens, max_seqlen: x is a packed batch (SelfAttention.forward);
+        everything but attention is token-major and takes it as it is."""
         if (x.is_cuda and x.dtype == torch.bfloat16 and attn_mask is None
+                and cu_seqlens is None
                 and self.attn.head_dim == 64 and x.shape[1] == 128 and p == 0
                 and attn_p == 0
                 and _os.environ.get("MPIAMD_LAYER_FUSED", "0") == "1"):
@@ -218,9 +264,12 @@ class BertLayer(nn.Module):
                 self.fc2.weight, self.fc2.bias,
                 self.ln2.weight.float(), self.ln2.bias.float())
             return y.view(b, s, h)
+        # a padded batch calls the attention exactly as before
+        pk = {} if cu_seqlens is None else {"cu_seqlens": cu_seqlens,
+                                            "max_seqlen": max_seqlen}
         x = self._join_ln(
-            self.ln1, x, self.attn(x, attn_mask, attn_p, rng, attn_site), p,
-            rng, site)
+            self.ln1, x, self.attn(x, attn_mask, attn_p, rng, attn_site, **pk),
+            p, rng, site)
         if x.is_cuda and x.dtype == torch.bfloat16:
             # fused FFN: GELU lives in the GEMM epilogues (fwd emits
             # h_pre + gelu(h); bwd's fc2-dx multiplies by gelu'(h_pre))
@@ -243,10 +292,17 @@ class BertEmbeddings(nn.Module):
         for e in (self.tok, self.pos, self.typ):
             nn.init.normal_(e.weight, std=0.02)
 
-    def forward(self, ids, type_ids=None, p=0.0, rng=None, site=0):
+    def forward(self, ids, type_ids=None, p=0.0, rng=None, site=0, *,
+                position_ids=None):
+        """position_ids (ids' shape): each token's position, for a packed
+        batch whose tokens count from 0 within their own sequence; default
+        0..s−1 along dim 1."""
         s = ids.shape[1]
-        pos = torch.arange(s, device=ids.device)
-        x = self.tok(ids) + self.pos(pos)[None]
+        if position_ids is None:
+            pos = self.pos(torch.arange(s, device=ids.device))[None]
+        else:
+            pos = self.pos(position_ids)
+        x = self.tok(ids) + pos
         if type_ids is not None:
             x = x + self.typ(type_ids)
         x = self.ln(x)
@@ -295,16 +351,38 @@ class BertModel(nn.Module):
             self._dropout_rng = rng
         return rng
 
-    def forward(self, ids, type_ids=None, attn_mask=None):
+    def forward(self, ids, type_ids=None, attn_mask=None, *, cu_seqlens=None,
+                max_seqlen=None, position_ids=None):
+        """cu_seqlens (int32 [N + 1] on ids' device): ids is a packed batch
+        [1, T] of N sequence slots back to back (pack_padded_batch) instead
+        of a padded [b, s] one; no attn_mask then. max_seqlen (host int,
+        default cfg.max_seq) bounds the sequence lengths, and position_ids
+        [1, T] gives each token its position within its own sequence. T, N
+        and max_seqlen fix every shape; the lengths live in cu_seqlens'
+        contents, so a captured step replays on another mix."""
+        pk = {}
+        if cu_seqlens is not None:
+            if attn_mask is not None:
+                raise ValueError("a packed batch (cu_seqlens) takes no "
+                                 "attn_mask")
+            if ids.dim() != 2 or ids.shape[0] != 1:
+                raise ValueError(f"packed ids must be [1, T], got "
+                                 f"{tuple(ids.shape)}")
+            if max_seqlen is None:
+                max_seqlen = self.cfg.max_seq
+            if not 1 <= max_seqlen <= self.cfg.max_seq:
+                raise ValueError(f"max_seqlen must be in [1, max_seq="
+                                 f"{self.cfg.max_seq}], got {max_seqlen}")
+            pk = {"cu_seqlens": cu_seqlens, "max_seqlen": int(max_seqlen)}
         if attn_mask is not None and attn_mask.dim() == 2:
             # (b, s) 1/0 mask → additive (b, 1, 1, s)
             attn_mask = (1.0 - attn_mask[:, None, None, :].float()) * torch.finfo(torch.float32).min
         p = self.cfg.dropout if self.training else 0.0
         pa = self.cfg.attn_dropout if self.training else 0.0
         if not (p > 0 or pa > 0):
-            x = self.embeddings(ids, type_ids)
+            x = self.embeddings(ids, type_ids, position_ids=position_ids)
             for layer in self.layers:
-                x = layer(x, attn_mask)
+                x = layer(x, attn_mask, **pk)
             return x
         # static call sites: embeddings 0, layer i attention-output join
         # 1 + 2i, FFN-output join 2 + 2i, attention probabilities
@@ -315,9 +393,11 @@ class BertModel(nn.Module):
             rng = self._rng(w.device)
             rng.tick()
         n = len(self.layers)
-        x = self.embeddings(ids, type_ids, p, rng, 0)
+        x = self.embeddings(ids, type_ids, p, rng, 0,
+                            position_ids=position_ids)
         for i, layer in enumerate(self.layers):
-            x = layer(x, attn_mask, p, rng, 1 + 2 * i, pa, 1 + 2 * n + i)
+            x = layer(x, attn_mask, p, rng, 1 + 2 * i, pa, 1 + 2 * n + i,
+                      **pk)
         return x
 
 
@@ -338,9 +418,24 @@ class BertForPreTraining(nn.Module):
         """BertModel.seed_dropout of the trunk."""
         self.bert.seed_dropout(seed)
 
+    def _first_tokens(self, x, cu_seqlens):
+        """The first token of every sequence (what NSP reads): x[:, 0] of a
+        padded batch; row cu_seqlens[n] of a packed one. An empty slot reads
+        a neighbour's row (clamped into the buffer) and carries nsp label
+        −100, which the NSP loss ignores."""
+        if cu_seqlens is None:
+            return x[:, 0]
+        return x[0, cu_seqlens[:-1].long().clamp(max=x.shape[1] - 1)]
+
     def forward(self, ids, type_ids=None, attn_mask=None, mlm_labels=None,
-                nsp_labels=None):
-        x = self.bert(ids, type_ids, attn_mask)
+                nsp_labels=None, *, cu_seqlens=None, max_seqlen=None,
+                position_ids=None):
+        """cu_seqlens, max_seqlen, position_ids: a packed batch, as in
+        BertModel.forward. mlm_labels is then [1, T] with −100 at the unused
+        tail, nsp_labels / nsp_logits have one entry per sequence slot, and
+        an empty slot's nsp label is −100."""
+        x = self.bert(ids, type_ids, attn_mask, cu_seqlens=cu_seqlens,
+                      max_seqlen=max_seqlen, position_ids=position_ids)
         h = self.mlm_ln(F.gelu(self.mlm_transform(x), approximate="tanh"))
         tok_w = self.bert.embeddings.tok.weight
         if mlm_labels is not None:
@@ -360,8 +455,9 @@ class BertForPreTraining(nn.Module):
                     mlm_labels.view(-1), ignore_index=-100)
             loss = l_mlm
             if nsp_labels is not None:
-                nsp_logits = self.nsp(x[:, 0])
-                loss = loss + F.cross_entropy(nsp_logits.float(), nsp_labels)
+                nsp_logits = self.nsp(self._first_tokens(x, cu_seqlens))
+                loss = loss + F.cross_entropy(nsp_logits.float(), nsp_labels,
+                                              ignore_index=-100)
             return loss
         if h.is_cuda and h.dtype == torch.bfloat16:
             # decoder GEMM on the in-tree NT kernel with the bias folded
@@ -371,7 +467,7 @@ class BertForPreTraining(nn.Module):
                                    self.mlm_bias).view(b, s, -1)
         else:
             mlm_logits = torch.matmul(h, tok_w.t().to(h.dtype)) + self.mlm_bias.to(h.dtype)
-        nsp_logits = self.nsp(x[:, 0])
+        nsp_logits = self.nsp(self._first_tokens(x, cu_seqlens))
         return mlm_logits, nsp_logits
 
     def loss(self, mlm_logits, nsp_logits, mlm_labels, nsp_labels):
@@ -387,6 +483,71 @@ class BertForPreTraining(nn.Module):
                 mlm_labels.view(-1), ignore_index=-100)
         l_nsp = F.cross_entropy(nsp_logits.float(), nsp_labels)
         return l_mlm + l_nsp
+
+
+class PackedBatch(NamedTuple):
+    """pack_padded_batch's result; the fields are BertForPreTraining.forward's
+    arguments of the same names."""
+    ids: torch.Tensor                      # [1, T]
+    type_ids: Optional[torch.Tensor]       # [1, T] or None
+    position_ids: torch.Tensor             # [1, T]
+    mlm_labels: Optional[torch.Tensor]     # [1, T] or None
+    cu_seqlens: torch.Tensor               # int32 [max_sequences + 1]
+    max_seqlen: int
+
+
+def pack_padded_batch(ids, type_ids, attn_mask, mlm_labels, token_budget=None,
+                      max_sequences=None, *, max_seq=None) -> PackedBatch:
+    """Drop the padding of a [b, s] batch: its valid tokens (attn_mask 1/0,
+    each row's valid tokens a prefix) back to back in one [1, T] row.
+
+    T = token_budget (default: the number of valid tokens); the unused tail
+    gets id 0, type 0, position 0 and label −100. cu_seqlens has
+    max_sequences + 1 entries (default b + 1), the slots past b empty, so
+    that batches of a data pipeline share one shape whatever their lengths.
+    position_ids count from 0 within each sequence; max_seqlen is the
+    longest length in this batch. type_ids and mlm_labels may be None.
+    Raises ValueError if the tokens exceed token_budget, the sequences
+    max_sequences, or a length max_seq (pass the model's cfg.max_seq).
+    A host-side data-pipeline helper: it reads the mask on the host."""
+    b, s = ids.shape
+    valid = attn_mask.to(torch.bool)
+    lens = valid.sum(dim=1)
+    if not torch.equal(valid, torch.arange(s, device=ids.device)[None]
+                       < lens[:, None]):
+        raise ValueError("attn_mask must mark a prefix of each row as valid")
+    lens_l = [int(n) for n in lens.tolist()]
+    total = sum(lens_l)
+    budget = total if token_budget is None else int(token_budget)
+    slots = b if max_sequences is None else int(max_sequences)
+    if total > budget:
+        raise ValueError(f"{total} valid tokens do not fit token_budget="
+                         f"{budget}")
+    if b > slots:
+        raise ValueError(f"{b} sequences do not fit max_sequences={slots}")
+    if budget < 1:
+        raise ValueError("token_budget must be at least 1")
+    longest = max(lens_l)
+    if max_seq is not None and longest > max_seq:
+        raise ValueError(f"a sequence of {longest} tokens exceeds max_seq="
+                         f"{max_seq}")
+
+    def pack(t, fill):
+        if t is None:
+            return None
+        out = t.new_full((1, budget), fill)
+        out[0, :total] = t[valid]
+        return out
+
+    pos = torch.arange(s, device=ids.device)[None].expand(b, s)
+    cu = [0]
+    for n in lens_l:
+        cu.append(cu[-1] + n)
+    cu += [total] * (slots - b)
+    return PackedBatch(
+        pack(ids, 0), pack(type_ids, 0), pack(pos, 0), pack(mlm_labels, -100),
+        torch.tensor(cu, dtype=torch.int32, device=ids.device),
+        max(longest, 1))
 
 
 def bert_param_groups(model: nn.Module, weight_decay: float = 0.01):

@@ -1310,6 +1310,134 @@ static Tensor flash_attn_drop_bwd_b(const Tensor &qkv, const Tensor &ctx,
   return dqkv;
 }
 
+// ------------------ packed (varlen) tiled attention ------------------
+// qkv [T,3,H,64]: N sequence slots back to back, cu_seqlens device int32
+// [N+1] (cu[0] = 0, non-decreasing, cu[N] <= T, no length above max_seqlen:
+// preconditions, never read on the host — nothing here syncs). Returns
+// (ctx [T,H*64], lse [H,T] fp32); rows at or past cu[N] are zeros.
+struct VarlenShape {
+  int N, T, H, max_seqlen;
+};
+static VarlenShape check_varlen_qkv(const Tensor &qkv, int64_t heads,
+                                    const Tensor &cu, int64_t max_seqlen) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16,
+              "qkv must be a bf16 GPU tensor");
+  TORCH_CHECK(qkv.dim() == 4 && qkv.size(1) == 3 && qkv.size(3) == 64 &&
+                  qkv.size(0) >= 1 && qkv.size(2) >= 1,
+              "qkv must be [T,3,H,64], got ", qkv.sizes());
+  TORCH_CHECK(qkv.is_contiguous(), "qkv must be contiguous");
+  TORCH_CHECK(heads < 0 || qkv.size(2) == heads, "qkv has ", qkv.size(2),
+              " heads, expected ", heads);
+  TORCH_CHECK(qkv.size(0) < (1L << 31), "T must fit an int32");
+  TORCH_CHECK(cu.is_cuda() && cu.device() == qkv.device() &&
+                  cu.scalar_type() == at::kInt && cu.dim() == 1 &&
+                  cu.is_contiguous() && cu.numel() >= 2,
+              "cu_seqlens must be a contiguous 1-D int32 tensor of at least "
+              "2 elements on qkv's GPU");
+  TORCH_CHECK(max_seqlen >= 1 && max_seqlen < (1L << 31),
+              "max_seqlen must be a positive int32, got ", max_seqlen);
+  long N = cu.numel() - 1;
+  TORCH_CHECK(N * qkv.size(2) < (1L << 31), "N*H must fit an int32");
+  return {(int)N, (int)qkv.size(0), (int)qkv.size(2), (int)max_seqlen};
+}
+
+static void check_varlen_ctx(const Tensor &t, const Tensor &qkv,
+                             const VarlenShape &d, const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == qkv.device() &&
+                  t.scalar_type() == at::kBFloat16 && t.is_contiguous() &&
+                  t.numel() == (long)d.T * d.H * 64,
+              name, " must be a contiguous bf16 [T,H*64] tensor on qkv's GPU");
+}
+
+static void check_varlen_lse(const Tensor &lse, const Tensor &qkv,
+                             const VarlenShape &d) {
+  TORCH_CHECK(lse.is_cuda() && lse.device() == qkv.device() &&
+                  lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.numel() == (long)d.H * d.T,
+              "lse must be a contiguous fp32 [H,T] tensor on qkv's GPU");
+}
+
+static void check_varlen_drop_shape(const VarlenShape &d) {
+  TORCH_CHECK(attn_dropout_shape_ok(d.N, d.H, d.max_seqlen),
+              "attention dropout: N*H*ceil(max_seqlen/16)*2*max_seqlen must "
+              "be below 2^32, got N=", d.N, " H=", d.H, " max_seqlen=",
+              d.max_seqlen);
+}
+
+static std::vector<Tensor> flash_attn_varlen_fwd(const Tensor &qkv,
+                                                 const Tensor &cu_seqlens,
+                                                 int64_t max_seqlen,
+                                                 int64_t heads, double scale) {
+  const VarlenShape d = check_varlen_qkv(qkv, heads, cu_seqlens, max_seqlen);
+  const HIPDeviceGuard guard(qkv.device());
+  Tensor ctx = at::empty({d.T, (long)d.H * 64}, qkv.options());
+  Tensor lse = at::empty({(long)d.H, d.T}, qkv.options().dtype(at::kFloat));
+  CHK(flash_attn_varlen_fwd_launch(
+      qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr<float>(),
+      cu_seqlens.data_ptr<int>(), d.N, d.T, d.max_seqlen, d.H, (float)scale,
+      cur_stream()));
+  return {ctx, lse};
+}
+
+static Tensor flash_attn_varlen_bwd(const Tensor &qkv, const Tensor &ctx,
+                                    const Tensor &dctx, const Tensor &lse,
+                                    const Tensor &cu_seqlens,
+                                    int64_t max_seqlen, double scale) {
+  const VarlenShape d = check_varlen_qkv(qkv, -1, cu_seqlens, max_seqlen);
+  check_varlen_ctx(ctx, qkv, d, "ctx");
+  check_varlen_ctx(dctx, qkv, d, "dctx");
+  check_varlen_lse(lse, qkv, d);
+  const HIPDeviceGuard guard(qkv.device());
+  Tensor delta = at::empty_like(lse);
+  Tensor dqkv = at::empty_like(qkv);
+  CHK(flash_attn_varlen_bwd_launch(
+      qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr<float>(),
+      delta.data_ptr<float>(), cu_seqlens.data_ptr<int>(), dqkv.data_ptr(),
+      d.N, d.T, d.max_seqlen, d.H, (float)scale, cur_stream()));
+  return dqkv;
+}
+
+static std::vector<Tensor> flash_attn_varlen_drop_fwd_b(
+    const Tensor &qkv, const Tensor &cu_seqlens, int64_t max_seqlen,
+    int64_t heads, double scale, const Tensor &state, double p,
+    int64_t site) {
+  const VarlenShape d = check_varlen_qkv(qkv, heads, cu_seqlens, max_seqlen);
+  check_varlen_drop_shape(d);
+  check_rng_state(state, qkv);
+  const DropParams dp = check_drop_params(p, site);
+  const HIPDeviceGuard guard(qkv.device());
+  Tensor ctx = at::empty({d.T, (long)d.H * 64}, qkv.options());
+  Tensor lse = at::empty({(long)d.H, d.T}, qkv.options().dtype(at::kFloat));
+  CHK(flash_attn_varlen_drop_fwd_launch(
+      qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr<float>(),
+      cu_seqlens.data_ptr<int>(), state.data_ptr<int64_t>(), dp.site, dp.thr,
+      dp.scale, d.N, d.T, d.max_seqlen, d.H, (float)scale, cur_stream()));
+  return {ctx, lse};
+}
+
+// state, p, site: what the forward was given (state unchanged since)
+static Tensor flash_attn_varlen_drop_bwd_b(
+    const Tensor &qkv, const Tensor &ctx, const Tensor &dctx,
+    const Tensor &lse, const Tensor &cu_seqlens, int64_t max_seqlen,
+    double scale, const Tensor &state, double p, int64_t site) {
+  const VarlenShape d = check_varlen_qkv(qkv, -1, cu_seqlens, max_seqlen);
+  check_varlen_drop_shape(d);
+  check_varlen_ctx(ctx, qkv, d, "ctx");
+  check_varlen_ctx(dctx, qkv, d, "dctx");
+  check_varlen_lse(lse, qkv, d);
+  check_rng_state(state, qkv);
+  const DropParams dp = check_drop_params(p, site);
+  const HIPDeviceGuard guard(qkv.device());
+  Tensor delta = at::empty_like(lse);
+  Tensor dqkv = at::empty_like(qkv);
+  CHK(flash_attn_varlen_drop_bwd_launch(
+      qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr<float>(),
+      delta.data_ptr<float>(), cu_seqlens.data_ptr<int>(),
+      state.data_ptr<int64_t>(), dp.site, dp.thr, dp.scale, dqkv.data_ptr(),
+      d.N, d.T, d.max_seqlen, d.H, (float)scale, cur_stream()));
+  return dqkv;
+}
+
 // ------------------------- fused FFN (GELU) -------------------------
 // fc1 forward with the bias+GELU in the epilogue: returns (g, h_pre)
 static std::vector<Tensor> linear_gelu_fwd(const Tensor &x, const Tensor &w,
@@ -1864,6 +1992,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_drop_bwd", &flash_attn_drop_bwd_b, py::arg("qkv"),
         py::arg("ctx"), py::arg("dctx"), py::arg("lse"), py::arg("scale"),
         py::arg("mask"), py::arg("state"), py::arg("p"), py::arg("site"));
+  m.def("flash_attn_varlen_fwd", &flash_attn_varlen_fwd, py::arg("qkv"),
+        py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("heads"),
+        py::arg("scale"));
+  m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd, py::arg("qkv"),
+        py::arg("ctx"), py::arg("dctx"), py::arg("lse"),
+        py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("scale"));
+  m.def("flash_attn_varlen_drop_fwd", &flash_attn_varlen_drop_fwd_b,
+        py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"),
+        py::arg("heads"), py::arg("scale"), py::arg("state"), py::arg("p"),
+        py::arg("site"));
+  m.def("flash_attn_varlen_drop_bwd", &flash_attn_varlen_drop_bwd_b,
+        py::arg("qkv"), py::arg("ctx"), py::arg("dctx"), py::arg("lse"),
+        py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("scale"),
+        py::arg("state"), py::arg("p"), py::arg("site"));
   m.def("linear_wgrad_only", &linear_wgrad_only);
   m.def("linear_gelu_dgrad", &linear_gelu_dgrad);
   m.def("masked_xent_bwd", &masked_xent_bwd);

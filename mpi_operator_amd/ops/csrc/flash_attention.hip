@@ -35,6 +35,28 @@
 //   dS = (rs·keep∘dP − delta)∘P·scale
 // m, l and lse are those of the undropped softmax, and delta = rowsum(dO∘O)
 // still equals rowsum(dP_eff∘P), so the delta kernel is shared.
+//
+// VARLEN (second template parameter of the three MFMA kernels): N sequences
+// packed back to back in one token-major buffer, no padding and no key mask.
+//   qkv / dqkv [T, 3, H, 64]; ctx / dctx [T, H·64]; lse / delta [H, T]
+//   (the dense layouts at B = 1, S = T, so the delta kernel serves as is);
+//   cu_seqlens int32 [N + 1] in DEVICE memory: sequence n owns rows
+//   cu[n] .. cu[n+1] − 1.
+// Block (n·H + h, y) reads its base row cu[n] and length L = cu[n+1] − cu[n]
+// and is then the dense block (b, h, y) of a [1, L] batch at that base: L
+// stands where S stands — bounds, key tiles, q-chunks — so tiles, their
+// order and every rounding are the dense kernel's. The grid's y extent is
+// sized by the host int max_seqlen; a workgroup whose chunk starts at or
+// past L (every block of an empty slot) returns before its first barrier,
+// the whole workgroup alike. Only the CONTENTS of cu_seqlens vary between
+// launches, so a captured graph replays on another length mix.
+// Preconditions, not checked on the device: cu[0] = 0, cu non-decreasing,
+// cu[N] <= T, and no L > max_seqlen (rows past max_seqlen would be left
+// zero). The base and end rows are clamped into [0, T], so cu_seqlens that
+// break them give wrong numbers but no access outside the buffers.
+// Rows at or past cu[N] belong to no block: the launchers zero ctx, lse
+// and dqkv ahead of the kernels (memset nodes under capture).
+// DROP keys the masks per sequence: see philox.h.
 #include "common.h"
 #include "launchers.h"
 #include "philox.h"
@@ -49,6 +71,32 @@ constexpr int FA_T = 128;   // q-chunk rows and key-tile width
 // and above finfo(float).min, so a masked score (≈ finfo.min) minus the
 // floor is still hugely negative and its exp is exactly 0
 constexpr float FA_FLOOR = -3.4e38f;
+
+// launch arguments of the VARLEN kernels (unused where VARLEN is false)
+struct FaVarlen {
+  const int *cu;  // [N + 1] device
+  int total;      // T: rows of the packed buffers
+  int max_seqlen; // the dropout masks' S (philox.h)
+};
+
+// where block row bh's sequence lives: first row in the token-major
+// buffers, offset of its lse / delta row, and its length
+struct FaSeq {
+  long tok0, lse0;
+  int S;
+};
+
+template <bool VARLEN>
+DEV_INLINE FaSeq fa_seq(int bh, int H, int S, const FaVarlen &vl) {
+  if constexpr (VARLEN) {
+    int n = bh / H, h = bh % H;
+    int c0 = min(max(vl.cu[n], 0), vl.total);
+    int c1 = min(max(vl.cu[n + 1], c0), vl.total);
+    return {(long)c0, (long)h * vl.total + c0, c1 - c0};
+  } else {
+    return {(long)(bh / H) * S, (long)bh * S, S};
+  }
+}
 
 DEV_INLINE bf16x8a fa_bf8(ushort8 u) {
   union { ushort8 u; bf16x8a b; } v;
@@ -149,16 +197,22 @@ DEV_INLINE float16a fa_nt_frag(const bf16x8a af[4], const ushort8 *img, int ni,
 // ------------------------------ forward ------------------------------
 // grid (B·H, ceil(S/128)); LDS K 16 KiB + V 16 KiB + P 32 KiB = 64 KiB
 // (2 workgroups per CU).
-template <bool DROP>
+// VARLEN: grid (N·H, ceil(max_seqlen/128)), B = N, S_ unused, no mask.
+template <bool DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
     const uint16_t *__restrict__ qkv, // [B, S, 3, H, 64]
     uint16_t *__restrict__ ctx,       // [B, S, H*64]
     float *__restrict__ lse,          // [B, H, S]
-    const float *__restrict__ mask,   // [B, S] additive (or nullptr)
-    int B, int S, int H, float scale, AttnDropArgs da) {
+    const float *__restrict__ mask_,  // [B, S] additive (or nullptr)
+    int B, int S_, int H, float scale, AttnDropArgs da, FaVarlen vl) {
   constexpr int D = FA_D, T = FA_T;
   int bh = blockIdx.x;
   int b = bh / H, h = bh % H;
+  const FaSeq sq = fa_seq<VARLEN>(bh, H, S_, vl);
+  const int S = sq.S;
+  // workgroup-uniform, ahead of the first barrier
+  if (VARLEN && (int)blockIdx.y * T >= S) return;
+  const float *mask = VARLEN ? nullptr : mask_;
   int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   __shared__ __align__(128) ushort8 k_img[T * 8];
@@ -166,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
   __shared__ __align__(128) uint16_t p_img[4][32][T];
 
   const long qkv_row = (long)3 * H * D;
-  const uint16_t *base = qkv + (long)b * S * qkv_row;
+  const uint16_t *base = qkv + sq.tok0 * qkv_row;
   const uint16_t *qp = base + h * D;
   const uint16_t *kp = base + (long)1 * H * D + h * D;
   const uint16_t *vp = base + (long)2 * H * D + h * D;
@@ -185,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
   }
   float16a oacc[2] = {};
   AttnDrop dr{};
-  if (DROP) dr = attn_drop_init(da, bh, S);
+  if (DROP) dr = attn_drop_init(da, bh, VARLEN ? vl.max_seqlen : S);
 
   const int nkt = (S + T - 1) / T;
   for (int kt = 0; kt < nkt; ++kt) {
@@ -294,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
   // ctx = O / l, lse = m + log(l). A row with no valid key at all has
   // l = 0: write zeros and lse = floor (finite) instead of 0/0.
   long crow = (long)H * D;
-  uint16_t *cp = ctx + (long)b * S * crow + h * D;
+  uint16_t *cp = ctx + sq.tok0 * crow + h * D;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     int row = qrow0 + fa_crow(r, lane);
@@ -305,7 +359,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
     for (int ni = 0; ni < 2; ++ni)
       cp[(long)row * crow + ni * 32 + (lane & 31)] = f2bf(oacc[ni][r] * inv);
     if ((lane & 31) == 0)
-      lse[(long)bh * S + row] = l > 0.f ? m_run[r] + __logf(l) : m_run[r];
+      lse[sq.lse0 + row] = l > 0.f ? m_run[r] + __logf(l) : m_run[r];
   }
 }
 
@@ -316,7 +370,7 @@ extern "C" hipError_t flash_attn_fwd_launch(const void *qkv, void *ctx,
   if (S < 1) return hipErrorInvalidValue;
   flash_attn_fwd_k<false><<<dim3(B * H, (S + FA_T - 1) / FA_T), 256, 0, strm>>>(
       (const uint16_t *)qkv, (uint16_t *)ctx, lse, mask, B, S, H, scale,
-      AttnDropArgs{});
+      AttnDropArgs{}, FaVarlen{});
   HIP_KERNEL_CHECK();
   return hipSuccess;
 }
@@ -328,9 +382,47 @@ extern "C" hipError_t flash_attn_drop_fwd_launch(
   if (S < 1 || !state) return hipErrorInvalidValue;
   flash_attn_fwd_k<true><<<dim3(B * H, (S + FA_T - 1) / FA_T), 256, 0, strm>>>(
       (const uint16_t *)qkv, (uint16_t *)ctx, lse, mask, B, S, H, scale,
-      AttnDropArgs{state, site, thr, rs});
+      AttnDropArgs{state, site, thr, rs}, FaVarlen{});
   HIP_KERNEL_CHECK();
   return hipSuccess;
+}
+
+// Packed forward: zero ctx and lse (the rows past cu[N] stay zero), then one
+// block row per (sequence slot, head).
+template <bool DROP>
+static hipError_t fa_varlen_fwd(const void *qkv, void *ctx, float *lse,
+                                const int *cu_seqlens, AttnDropArgs da, int N,
+                                int T, int max_seqlen, int H, float scale,
+                                hipStream_t strm) {
+  if (N < 1 || T < 1 || max_seqlen < 1 || H < 1 || !cu_seqlens)
+    return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(ctx, 0, (size_t)T * H * FA_D * 2, strm);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(lse, 0, (size_t)T * H * sizeof(float), strm);
+  if (e != hipSuccess) return e;
+  dim3 grid(N * H, (max_seqlen + FA_T - 1) / FA_T);
+  flash_attn_fwd_k<DROP, true><<<grid, 256, 0, strm>>>(
+      (const uint16_t *)qkv, (uint16_t *)ctx, lse, nullptr, N, 0, H, scale, da,
+      FaVarlen{cu_seqlens, T, max_seqlen});
+  HIP_KERNEL_CHECK();
+  return hipSuccess;
+}
+
+extern "C" hipError_t flash_attn_varlen_fwd_launch(
+    const void *qkv, void *ctx, float *lse, const int *cu_seqlens, int N, int T,
+    int max_seqlen, int H, float scale, hipStream_t strm) {
+  return fa_varlen_fwd<false>(qkv, ctx, lse, cu_seqlens, AttnDropArgs{}, N, T,
+                              max_seqlen, H, scale, strm);
+}
+
+extern "C" hipError_t flash_attn_varlen_drop_fwd_launch(
+    const void *qkv, void *ctx, float *lse, const int *cu_seqlens,
+    const int64_t *state, uint32_t site, uint32_t thr, float rs, int N, int T,
+    int max_seqlen, int H, float scale, hipStream_t strm) {
+  if (!state) return hipErrorInvalidValue;
+  return fa_varlen_fwd<true>(qkv, ctx, lse, cu_seqlens,
+                             AttnDropArgs{state, site, thr, rs}, N, T,
+                             max_seqlen, H, scale, strm);
 }
 
 // ------------------------------ backward ------------------------------
@@ -367,7 +459,12 @@ __global__ __launch_bounds__(256) void flash_attn_delta_k(
 // DROP: the forward's keep bits are drawn again (band0 = global row of the
 // wave's first q-row >> 4, gcol = this lane's global key column): the p16
 // image takes p·keep and dS = (dp·keep·rs − delta)·p·scale.
-template <bool DROP>
+// ROWINF: the caller passes lse_r = +inf for rows >= S instead, so that
+// exp(0 − inf) = 0 gives those rows' exact zeros and `rok` is not read; the
+// 16 row predicates then need not stay live in SGPR pairs across the call
+// (the VARLEN dK/dV kernel spilled SGPRs without it). Valid rows are
+// computed exactly as with ROWINF = false.
+template <bool DROP, bool ROWINF = false>
 DEV_INLINE void fa_pds_frag(const bf16x8a qf[4], const bf16x8a dof[4],
                             const ushort8 *k_nt, const ushort8 *v_nt, int ni,
                             int lane, int sqw, bool cok, float mk,
@@ -383,7 +480,8 @@ DEV_INLINE void fa_pds_frag(const bf16x8a qf[4], const bf16x8a dof[4],
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     int row = sqw + fa_crow(r, lane);
-    float p = (cok && rok[r]) ? __expf(s[r] * scale + mk - lse_r[r]) : 0.f;
+    float p = (cok && (ROWINF || rok[r]))
+                  ? __expf(s[r] * scale + mk - lse_r[r]) : 0.f;
     float dpe = dp[r], pk = p;
     if (DROP) {
       bool keep = (kb >> r) & 1u;
@@ -400,20 +498,26 @@ DEV_INLINE void fa_pds_frag(const bf16x8a qf[4], const bf16x8a dof[4],
 // dK, dV: grid (B·H, ceil(S/128)) over key chunks, loop over q-chunks.
 // LDS: K, V (NT, staged once) + Q, dO (subtile, per q-chunk) 4×16 KiB
 // + P, dS 2×32 KiB = 128 KiB.
-template <bool DROP>
+// VARLEN: grid (N·H, ceil(max_seqlen/128)), B = N, S_ unused, no mask.
+template <bool DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
     const uint16_t *__restrict__ qkv,   // [B, S, 3, H, 64]
     const uint16_t *__restrict__ dctx,  // [B, S, H*64]
     const float *__restrict__ lse,      // [B, H, S]
     const float *__restrict__ delta,    // [B, H, S]
-    const float *__restrict__ mask,     // [B, S] or nullptr
+    const float *__restrict__ mask_,    // [B, S] or nullptr
     uint16_t *__restrict__ dqkv,        // [B, S, 3, H, 64]
-    int B, int S, int H, float scale, AttnDropArgs da) {
+    int B, int S_, int H, float scale, AttnDropArgs da, FaVarlen vl) {
   constexpr int D = FA_D, T = FA_T;
   int bh = blockIdx.x;
   int b = bh / H, h = bh % H;
-  int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const FaSeq sq = fa_seq<VARLEN>(bh, H, S_, vl);
+  const int S = sq.S;
   const int kc0 = blockIdx.y * T;
+  // workgroup-uniform, ahead of the first barrier
+  if (VARLEN && kc0 >= S) return;
+  const float *mask = VARLEN ? nullptr : mask_;
+  int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   __shared__ __align__(128) ushort8 k_nt[T * 8];
   __shared__ __align__(128) ushort8 v_nt[T * 8];
@@ -423,13 +527,13 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
   __shared__ __align__(128) ushort8 ds_tr[T * 16];
 
   const long qrow = (long)3 * H * D, crow = (long)H * D;
-  const uint16_t *base = qkv + (long)b * S * qrow;
+  const uint16_t *base = qkv + sq.tok0 * qrow;
   const uint16_t *qp = base + h * D;
   const uint16_t *kp = base + (long)H * D + h * D;
   const uint16_t *vp = base + (long)2 * H * D + h * D;
-  const uint16_t *dop = dctx + (long)b * S * crow + h * D;
-  const float *lsep = lse + (long)bh * S;
-  const float *delp = delta + (long)bh * S;
+  const uint16_t *dop = dctx + sq.tok0 * crow + h * D;
+  const float *lsep = lse + sq.lse0;
+  const float *delp = delta + sq.lse0;
 
   fa_stage_nt(k_nt, kp, qrow, kc0, S, tid);
   fa_stage_nt(v_nt, vp, qrow, kc0, S, tid);
@@ -447,7 +551,7 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
   const int sqw = wave * 32; // recompute: q-rows; accumulate: key rows
   float16a dk[2] = {}, dv[2] = {};
   AttnDrop dr{};
-  if (DROP) dr = attn_drop_init(da, bh, S);
+  if (DROP) dr = attn_drop_init(da, bh, VARLEN ? vl.max_seqlen : S);
   const int nqc = (S + T - 1) / T;
   for (int qc = 0; qc < nqc; ++qc) {
     const int q0 = qc * T;
@@ -467,15 +571,16 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
     for (int r = 0; r < 16; ++r) {
       int row = q0 + sqw + fa_crow(r, lane);
       rok[r] = row < S;
-      lse_r[r] = rok[r] ? lsep[row] : 0.f;
+      // VARLEN: rows >= S get P = exp(0 − inf) = 0 (fa_pds_frag ROWINF)
+      lse_r[r] = rok[r] ? lsep[row] : (VARLEN ? INFINITY : 0.f);
       delta_r[r] = rok[r] ? delp[row] : 0.f;
     }
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni)
-      fa_pds_frag<DROP>(qf, dof, k_nt, v_nt, ni, lane, sqw, cok[ni], mk[ni],
-                        lse_r, delta_r, rok, scale, (uint16_t *)p_tr,
-                        (uint16_t *)ds_tr, dr, (uint32_t)(q0 + sqw) >> 4,
-                        kc0 + ni * 32 + (lane & 31));
+      fa_pds_frag<DROP, VARLEN>(
+          qf, dof, k_nt, v_nt, ni, lane, sqw, cok[ni], mk[ni], lse_r, delta_r,
+          rok, scale, (uint16_t *)p_tr, (uint16_t *)ds_tr, dr,
+          (uint32_t)(q0 + sqw) >> 4, kc0 + ni * 32 + (lane & 31));
     __syncthreads();
 
     // dK += dSᵀ·Q, dV += Pᵀ·dO: rows = this wave's 32 keys, k = the 128 q
@@ -495,7 +600,7 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
     }
   }
 
-  uint16_t *dk_out = dqkv + (long)b * S * qrow + (long)H * D + h * D;
+  uint16_t *dk_out = dqkv + sq.tok0 * qrow + (long)H * D + h * D;
   uint16_t *dv_out = dk_out + (long)H * D;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -514,17 +619,23 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
 // LDS: K, V (NT) + K (subtile) 3×16 KiB + dS 32 KiB = 80 KiB. The dS image
 // is written and read by the same wave (its own 32 q-rows = 8 private row
 // blocks), so it needs a wave-level fence only.
-template <bool DROP>
+// VARLEN: grid (N·H, ceil(max_seqlen/128)), B = N, S_ unused, no mask.
+template <bool DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
     const uint16_t *__restrict__ qkv, const uint16_t *__restrict__ dctx,
     const float *__restrict__ lse, const float *__restrict__ delta,
-    const float *__restrict__ mask, uint16_t *__restrict__ dqkv, int B, int S,
-    int H, float scale, AttnDropArgs da) {
+    const float *__restrict__ mask_, uint16_t *__restrict__ dqkv, int B,
+    int S_, int H, float scale, AttnDropArgs da, FaVarlen vl) {
   constexpr int D = FA_D, T = FA_T;
   int bh = blockIdx.x;
   int b = bh / H, h = bh % H;
-  int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const FaSeq sq = fa_seq<VARLEN>(bh, H, S_, vl);
+  const int S = sq.S;
   const int q0 = blockIdx.y * T;
+  // workgroup-uniform, ahead of the first barrier
+  if (VARLEN && q0 >= S) return;
+  const float *mask = VARLEN ? nullptr : mask_;
+  int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   __shared__ __align__(128) ushort8 k_nt[T * 8];
   __shared__ __align__(128) ushort8 v_nt[T * 8];
@@ -532,13 +643,13 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
   __shared__ __align__(128) ushort8 ds_tr[T * 16];
 
   const long qrow = (long)3 * H * D, crow = (long)H * D;
-  const uint16_t *base = qkv + (long)b * S * qrow;
+  const uint16_t *base = qkv + sq.tok0 * qrow;
   const uint16_t *qp = base + h * D;
   const uint16_t *kp = base + (long)H * D + h * D;
   const uint16_t *vp = base + (long)2 * H * D + h * D;
-  const uint16_t *dop = dctx + (long)b * S * crow + h * D;
-  const float *lsep = lse + (long)bh * S;
-  const float *delp = delta + (long)bh * S;
+  const uint16_t *dop = dctx + sq.tok0 * crow + h * D;
+  const float *lsep = lse + sq.lse0;
+  const float *delp = delta + sq.lse0;
 
   const int sqw = wave * 32;
   bf16x8a qf[4], dof[4];
@@ -556,7 +667,7 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
 
   float16a dq[2] = {};
   AttnDrop dr{};
-  if (DROP) dr = attn_drop_init(da, bh, S);
+  if (DROP) dr = attn_drop_init(da, bh, VARLEN ? vl.max_seqlen : S);
   const int nkt = (S + T - 1) / T;
   for (int kt = 0; kt < nkt; ++kt) {
     const int k0 = kt * T;
@@ -593,7 +704,7 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
     }
   }
 
-  uint16_t *dq_out = dqkv + (long)b * S * qrow + h * D;
+  uint16_t *dq_out = dqkv + sq.tok0 * qrow + h * D;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     int row = q0 + sqw + fa_crow(r, lane);
@@ -616,11 +727,11 @@ extern "C" hipError_t flash_attn_bwd_launch(
   dim3 grid(B * H, (S + FA_T - 1) / FA_T);
   flash_attn_bwd_dkv_k<false><<<grid, 256, 0, strm>>>(
       (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale, AttnDropArgs{});
+      (uint16_t *)dqkv, B, S, H, scale, AttnDropArgs{}, FaVarlen{});
   HIP_KERNEL_CHECK();
   flash_attn_bwd_dq_k<false><<<grid, 256, 0, strm>>>(
       (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale, AttnDropArgs{});
+      (uint16_t *)dqkv, B, S, H, scale, AttnDropArgs{}, FaVarlen{});
   HIP_KERNEL_CHECK();
   return hipSuccess;
 }
@@ -640,11 +751,63 @@ extern "C" hipError_t flash_attn_drop_bwd_launch(
   AttnDropArgs da{state, site, thr, rs};
   flash_attn_bwd_dkv_k<true><<<grid, 256, 0, strm>>>(
       (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale, da);
+      (uint16_t *)dqkv, B, S, H, scale, da, FaVarlen{});
   HIP_KERNEL_CHECK();
   flash_attn_bwd_dq_k<true><<<grid, 256, 0, strm>>>(
       (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale, da);
+      (uint16_t *)dqkv, B, S, H, scale, da, FaVarlen{});
   HIP_KERNEL_CHECK();
   return hipSuccess;
+}
+
+// Packed backward: delta over all T rows (the dense kernel at B = 1, S = T;
+// ctx is zero past cu[N], so delta is too), dqkv zeroed for the rows past
+// cu[N], then dK/dV and dQ with one block row per (sequence slot, head).
+template <bool DROP>
+static hipError_t fa_varlen_bwd(const void *qkv, const void *ctx,
+                                const void *dctx, const float *lse,
+                                float *delta, const int *cu_seqlens,
+                                AttnDropArgs da, void *dqkv, int N, int T,
+                                int max_seqlen, int H, float scale,
+                                hipStream_t strm) {
+  if (N < 1 || T < 1 || max_seqlen < 1 || H < 1 || !cu_seqlens)
+    return hipErrorInvalidValue;
+  long nthr = (long)T * H * 8;
+  flash_attn_delta_k<<<cdiv_h(nthr, 256), 256, 0, strm>>>(
+      (const uint16_t *)ctx, (const uint16_t *)dctx, delta, 1, T, H);
+  HIP_KERNEL_CHECK();
+  hipError_t e = hipMemsetAsync(dqkv, 0, (size_t)T * 3 * H * FA_D * 2, strm);
+  if (e != hipSuccess) return e;
+  dim3 grid(N * H, (max_seqlen + FA_T - 1) / FA_T);
+  FaVarlen vl{cu_seqlens, T, max_seqlen};
+  flash_attn_bwd_dkv_k<DROP, true><<<grid, 256, 0, strm>>>(
+      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, nullptr,
+      (uint16_t *)dqkv, N, 0, H, scale, da, vl);
+  HIP_KERNEL_CHECK();
+  flash_attn_bwd_dq_k<DROP, true><<<grid, 256, 0, strm>>>(
+      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, nullptr,
+      (uint16_t *)dqkv, N, 0, H, scale, da, vl);
+  HIP_KERNEL_CHECK();
+  return hipSuccess;
+}
+
+extern "C" hipError_t flash_attn_varlen_bwd_launch(
+    const void *qkv, const void *ctx, const void *dctx, const float *lse,
+    float *delta, const int *cu_seqlens, void *dqkv, int N, int T,
+    int max_seqlen, int H, float scale, hipStream_t strm) {
+  return fa_varlen_bwd<false>(qkv, ctx, dctx, lse, delta, cu_seqlens,
+                              AttnDropArgs{}, dqkv, N, T, max_seqlen, H, scale,
+                              strm);
+}
+
+// state, site, thr, rs: those of the forward; the masks are drawn again
+extern "C" hipError_t flash_attn_varlen_drop_bwd_launch(
+    const void *qkv, const void *ctx, const void *dctx, const float *lse,
+    float *delta, const int *cu_seqlens, const int64_t *state, uint32_t site,
+    uint32_t thr, float rs, void *dqkv, int N, int T, int max_seqlen, int H,
+    float scale, hipStream_t strm) {
+  if (!state) return hipErrorInvalidValue;
+  return fa_varlen_bwd<true>(qkv, ctx, dctx, lse, delta, cu_seqlens,
+                             AttnDropArgs{state, site, thr, rs}, dqkv, N, T,
+                             max_seqlen, H, scale, strm);
 }

@@ -179,6 +179,32 @@ hipError_t flash_attn_drop_bwd_launch(const void *qkv, const void *ctx,
                                       uint32_t thr, float rs, void *dqkv,
                                       int B, int S, int H, float scale,
                                       hipStream_t strm);
+// packed ("varlen") forms: N sequence slots back to back in T-row buffers,
+// qkv/dqkv [T,3,H,64], ctx/dctx [T,H*64], lse/delta [H,T], cu_seqlens device
+// int32 [N+1] (cu[0] = 0, non-decreasing, cu[N] <= T, no length above
+// max_seqlen: documented, not checked). max_seqlen sizes the grid only.
+// ctx, lse and dqkv rows at or past cu[N] are written as zeros.
+hipError_t flash_attn_varlen_fwd_launch(const void *qkv, void *ctx, float *lse,
+                                        const int *cu_seqlens, int N, int T,
+                                        int max_seqlen, int H, float scale,
+                                        hipStream_t strm);
+hipError_t flash_attn_varlen_bwd_launch(const void *qkv, const void *ctx,
+                                        const void *dctx, const float *lse,
+                                        float *delta, const int *cu_seqlens,
+                                        void *dqkv, int N, int T,
+                                        int max_seqlen, int H, float scale,
+                                        hipStream_t strm);
+// with dropout on P: sequence n draws the masks of batch row n of a dense
+// [N, max_seqlen] batch (philox.h)
+hipError_t flash_attn_varlen_drop_fwd_launch(
+    const void *qkv, void *ctx, float *lse, const int *cu_seqlens,
+    const int64_t *state, uint32_t site, uint32_t thr, float rs, int N, int T,
+    int max_seqlen, int H, float scale, hipStream_t strm);
+hipError_t flash_attn_varlen_drop_bwd_launch(
+    const void *qkv, const void *ctx, const void *dctx, const float *lse,
+    float *delta, const int *cu_seqlens, const int64_t *state, uint32_t site,
+    uint32_t thr, float rs, void *dqkv, int N, int T, int max_seqlen, int H,
+    float scale, hipStream_t strm);
 
 // ---- gemm.hip ----
 hipError_t gemm_nt(const void *a, const void *b, void *c, int M, int N, int K,

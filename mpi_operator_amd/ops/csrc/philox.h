@@ -81,6 +81,17 @@ DEV_INLINE uint32_t drop_keep8(const DropState &st, uint32_t site,
 // (row (r&3) + 8·(r>>2) + 4·(lane>>5) of the wave's 32, column lane&31) in
 // registers r = 8k..8k+7, k the band within the wave's rows, with slot =
 // r & 7 and half = lane >> 5. No draw is wasted and no lane exchanges bits.
+//
+// Packed (varlen) batches — N sequence slots in one [T, ...] buffer, lengths
+// in cu_seqlens, grid sized by max_seqlen — use the SAME scheme with
+//   bh = n·H + h (n the slot), S = max_seqlen (so NB = ceil(max_seqlen/16)),
+//   i, j = row and column WITHIN the sequence (0 .. L−1), not packed rows.
+// So element (i, j) of sequence n, head h draws the bit that a dense
+// [N, max_seqlen] batch draws for (b = n, h, i, j): attn_dropout_keep(seed,
+// offset, site, N, H, max_seqlen, p)[n, h, :L, :L] is its mask. Calls of
+// different slots are disjoint whatever the lengths are, the masks do not
+// depend on where a sequence sits in the buffer, and the host checks
+// attn_dropout_shape_ok(N, H, max_seqlen).
 struct AttnDrop {
   DropState st;
   uint32_t site, thr;

@@ -630,6 +630,90 @@ def flash_attention(qkv, heads, scale, mask=None, p: float = 0.0, rng=None,
                                       site)
 
 
+class FlashAttentionVarlenFn(torch.autograd.Function):
+    """FlashAttentionFn over a packed batch (the VARLEN kernels of
+    ops/csrc/flash_attention.hip): qkv [T, 3, H, 64] holds the sequences back
+    to back, cu_seqlens (int32 [N + 1], on qkv's device) their bounds.
+    Saves qkv, ctx, lse [H, T] and cu_seqlens; cu_seqlens is read on the
+    device only, so nothing syncs and a captured call replays on new lengths.
+    → ctx [T, H·64]."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, heads, scale):
+        qkv = qkv.contiguous()
+        if qkv.is_cuda and qkv.dtype == torch.bfloat16:
+            out, lse = hip_ext().flash_attn_varlen_fwd(qkv, cu_seqlens,
+                                                       max_seqlen, heads, scale)
+        else:
+            out, lse = ref.flash_attention_varlen_fwd(qkv, cu_seqlens,
+                                                      max_seqlen, heads, scale)
+        ctx.save_for_backward(qkv, out, lse, cu_seqlens)
+        ctx.scale, ctx.max_seqlen = scale, max_seqlen
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, cu_seqlens = ctx.saved_tensors
+        if qkv.is_cuda and qkv.dtype == torch.bfloat16:
+            dqkv = hip_ext().flash_attn_varlen_bwd(
+                qkv, out, dout.contiguous(), lse, cu_seqlens, ctx.max_seqlen,
+                ctx.scale)
+        else:
+            dqkv = ref.flash_attention_varlen_bwd(
+                qkv, out, dout, lse, cu_seqlens, ctx.max_seqlen, ctx.scale)
+        return dqkv, None, None, None, None
+
+
+class FlashAttentionVarlenDropFn(torch.autograd.Function):
+    """FlashAttentionVarlenFn with dropout on the probabilities; the state
+    clone and the redrawn masks are those of FlashAttentionDropFn."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, heads, scale, p, state,
+                site):
+        qkv = qkv.contiguous()
+        state = state.clone()
+        out, lse = hip_ext().flash_attn_varlen_drop_fwd(
+            qkv, cu_seqlens, max_seqlen, heads, scale, state, p, site)
+        ctx.save_for_backward(qkv, out, lse, cu_seqlens, state)
+        ctx.scale, ctx.max_seqlen, ctx.p, ctx.site = scale, max_seqlen, p, site
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, cu_seqlens, state = ctx.saved_tensors
+        dqkv = hip_ext().flash_attn_varlen_drop_bwd(
+            qkv, out, dout.contiguous(), lse, cu_seqlens, ctx.max_seqlen,
+            ctx.scale, state, ctx.p, ctx.site)
+        return (dqkv,) + (None,) * 7
+
+
+def flash_attention_varlen(qkv, cu_seqlens, max_seqlen, heads, scale,
+                           p: float = 0.0, rng=None, site: int = 0):
+    """Self-attention over a packed, unpadded batch: qkv [T, 3, H, 64] holds
+    N sequences back to back, sequence n in rows cu_seqlens[n] ..
+    cu_seqlens[n+1] − 1, each attending to itself only → ctx [T, H·64].
+
+    cu_seqlens: int32 [N + 1] on qkv's device with cu[0] = 0, non-decreasing
+    (an empty slot repeats a value) and cu[N] <= T; max_seqlen: a host int no
+    sequence exceeds — it sizes the kernels' grid and keys the dropout
+    masks. Neither is checked on the GPU, where nothing reads cu_seqlens on
+    the host: shapes depend on T, N and max_seqlen only, so a captured call
+    replays on other lengths written into cu_seqlens in place.
+    Rows at or past cu[N] (the unused tail of a token budget) come back as
+    zeros, and so do their gradients.
+    CUDA bf16 runs the HIP kernels; anything else the fp32 reference.
+    p > 0 (GPU bf16 only): sequence n draws the masks a dense
+    [N, max_seqlen] batch draws for batch row n (reference.
+    varlen_attn_dropout_keep)."""
+    if p == 0:
+        return FlashAttentionVarlenFn.apply(qkv, cu_seqlens, max_seqlen, heads,
+                                            scale)
+    _check_attn_dropout(qkv, p, rng)
+    return FlashAttentionVarlenDropFn.apply(qkv, cu_seqlens, max_seqlen, heads,
+                                            scale, p, rng.state, site)
+
+
 class BertLayerFn(torch.autograd.Function):
     """One whole transformer encoder layer (fused QKV → attention →
     out-proj → LN-join → FFN(GELU) → LN-join) as a single autograd node,

@@ -286,6 +286,61 @@ def flash_attention_bwd(qkv, ctx, dctx, lse, scale: float, mask=None,
     return dqkv.to(qkv.dtype)
 
 
+def _varlen_bounds(cu_seqlens, total: int):
+    """cu_seqlens → python ints, with the kernels' preconditions checked
+    (the reference may read them on the host; the kernels never do)."""
+    cu = [int(c) for c in cu_seqlens.tolist()]
+    if len(cu) < 2 or cu[0] != 0 or cu[-1] > total or any(
+            b < a for a, b in zip(cu, cu[1:])):
+        raise ValueError(f"cu_seqlens must start at 0, not decrease and end "
+                         f"at or below T={total}, got {cu}")
+    return cu
+
+
+def flash_attention_varlen_fwd(qkv, cu_seqlens, max_seqlen: int, heads: int,
+                               scale: float, keep=None,
+                               drop_scale: float = 1.0):
+    """Specification of the packed (varlen) forward. qkv [T,3,H,D] holds
+    N = len(cu_seqlens) − 1 sequences back to back, sequence n in rows
+    cu[n]..cu[n+1]−1 → (ctx [T,H·D] in qkv's dtype, lse [H,T] fp32): each
+    sequence is flash_attention_fwd of its own slice as a [1,L] batch, empty
+    slots contribute nothing, rows at or past cu[N] are zeros.
+    keep: optional list of N bool [H,L,L] masks (None for an empty slot),
+    see varlen_attn_dropout_keep."""
+    T, _, H, D = qkv.shape
+    cu = _varlen_bounds(cu_seqlens, T)
+    ctx = qkv.new_zeros(T, H * D)
+    lse = torch.zeros(H, T, dtype=torch.float32, device=qkv.device)
+    for n, (a, b) in enumerate(zip(cu, cu[1:])):
+        if b == a:
+            continue
+        if b - a > max_seqlen:
+            raise ValueError(f"sequence {n} has {b - a} > max_seqlen rows")
+        kn = keep[n][None] if keep is not None else None
+        c, l = flash_attention_fwd(qkv[a:b][None], heads, scale, None, kn,
+                                   drop_scale)
+        ctx[a:b], lse[:, a:b] = c[0], l[0]
+    return ctx, lse
+
+
+def flash_attention_varlen_bwd(qkv, ctx, dctx, lse, cu_seqlens,
+                               max_seqlen: int, scale: float, keep=None,
+                               drop_scale: float = 1.0):
+    """Specification of the packed backward: flash_attention_bwd per
+    sequence slice. Returns dqkv [T,3,H,D], zeros at or past cu[N]."""
+    T, _, H, D = qkv.shape
+    cu = _varlen_bounds(cu_seqlens, T)
+    dqkv = torch.zeros_like(qkv)
+    for n, (a, b) in enumerate(zip(cu, cu[1:])):
+        if b == a:
+            continue
+        kn = keep[n][None] if keep is not None else None
+        dqkv[a:b] = flash_attention_bwd(
+            qkv[a:b][None], ctx[a:b][None], dctx[a:b][None],
+            lse[:, a:b][None], scale, None, kn, drop_scale)[0]
+    return dqkv
+
+
 # ---------------------------------------------------------------- dropout
 # The random-number scheme of csrc/philox.h, bit for bit, on the CPU.
 PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
@@ -402,3 +457,20 @@ def attn_dropout_keep(seed: int, offset: int, site: int, B: int, H: int,
     r = (word >> (16 * (slot & 1)).astype(np.uint32)) & np.uint32(0xFFFF)
     keep = r >= np.uint32(thr)
     return torch.from_numpy(np.ascontiguousarray(keep.reshape(B, H, S, S)))
+
+
+def varlen_attn_dropout_keep(seed: int, offset: int, site: int, cu_seqlens,
+                             H: int, max_seqlen: int, p: float):
+    """The keep masks of a packed (varlen) batch: a list of N bool [H,L,L]
+    tensors (None for an empty slot). csrc/philox.h keys sequence n as batch
+    row n of a dense [N, max_seqlen] batch with rows and columns counted
+    within the sequence, so mask n is
+    attn_dropout_keep(seed, offset, site, N, H, max_seqlen, p)[n, :, :L, :L]."""
+    cu = [int(c) for c in cu_seqlens.tolist()]
+    N = len(cu) - 1
+    lens = [b - a for a, b in zip(cu, cu[1:])]
+    if max(lens) > max_seqlen:
+        raise ValueError(f"a sequence is longer than max_seqlen={max_seqlen}")
+    dense = attn_dropout_keep(seed, offset, site, N, H, max_seqlen, p)
+    return [dense[n, :, :L, :L].clone() if L else None
+            for n, L in enumerate(lens)]
