@@ -31,6 +31,13 @@ import os as _os
 _FUSED_LN = _os.environ.get("MPIAMD_FUSED_LN", "1") == "1"
 
 
+# MPIAMD_FUSED_EMBED: BertEmbeddings on the one-pass gather+sum+LN(+dropout)
+# kernel and the deterministic table-gradient kernels (ops/csrc/embedding.hip)
+# for GPU bf16 weights; 0 restores the torch gathers and adds ahead of the
+# fused LN. It rides on MPIAMD_FUSED_LN: with that off the chain is torch's.
+_FUSED_EMBED = _os.environ.get("MPIAMD_FUSED_EMBED", "1") == "1"
+
+
 # MPIAMD_FLASH_ATTN (read per call): route seq > 256 and key-masked
 # attention through ops/csrc/flash_attention.hip instead of the eager chain.
 # Default ON: 330 vs 230 seq/s and 6.9 vs 11.6 GiB peak at BERT-Large
@@ -297,6 +304,19 @@ class BertEmbeddings(nn.Module):
         """position_ids (ids' shape): each token's position, for a packed
         batch whose tokens count from 0 within their own sequence; default
         0..s−1 along dim 1."""
+        w = self.tok.weight
+        if (_FUSED_EMBED and _FUSED_LN and ids.is_cuda and w.is_cuda
+                and w.dtype == torch.bfloat16):
+            # the kernel reads one index width: the others follow ids. Without
+            # an rng the dropout stays _dropout's (torch's generator), applied
+            # to the fused block's output as the chain applied it to LN's.
+            same = lambda t: None if t is None else t.to(ids.dtype)
+            fp = p if rng is not None else 0.0
+            x = Fx.embed_layer_norm(
+                ids, w, self.pos.weight, self.typ.weight,
+                self.ln.weight.float(), self.ln.bias.float(), self.ln.eps,
+                same(type_ids), same(position_ids), fp, rng, site)
+            return _dropout(x, p, rng, site) if p > fp else x
         s = ids.shape[1]
         if position_ids is None:
             pos = self.pos(torch.arange(s, device=ids.device))[None]

@@ -925,6 +925,148 @@ static std::vector<Tensor> layernorm_drop_add_bwd(
   return {da, db, dgb.narrow(0, 0, N), dgb.narrow(0, N, N)};
 }
 
+// ------------------------- embedding -------------------------
+// bf16 [rows][N] table on the GPU, N a positive multiple of 8
+static void check_embed_table(const Tensor &w, const Tensor &like,
+                              const char *name) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 &&
+                  w.is_contiguous() && w.dim() == 2 && w.size(0) >= 1,
+              name, " must be a contiguous bf16 [rows][N] GPU tensor");
+  TORCH_CHECK(w.size(1) % 8 == 0 && w.size(1) >= 8, name,
+              ": N must be a positive multiple of 8, got ", w.size(1));
+  TORCH_CHECK(w.device() == like.device() && w.size(1) == like.size(-1), name,
+              " must share the first table's device and width");
+}
+
+static void check_embed_idx(const Tensor &idx, const Tensor &like,
+                            const Tensor &table, const char *name) {
+  TORCH_CHECK(idx.is_cuda() && idx.device() == table.device() &&
+                  idx.is_contiguous() && idx.numel() >= 1 &&
+                  (idx.scalar_type() == at::kLong ||
+                   idx.scalar_type() == at::kInt),
+              name, " must be a non-empty contiguous int32/int64 tensor on "
+              "the tables' GPU");
+  TORCH_CHECK(idx.sizes() == like.sizes() &&
+                  idx.scalar_type() == like.scalar_type(),
+              name, " must have the shape and dtype of ids");
+}
+
+static std::vector<int64_t> embed_out_shape(const Tensor &ids, int64_t N) {
+  std::vector<int64_t> shape(ids.sizes().begin(), ids.sizes().end());
+  shape.push_back(N);
+  return shape;
+}
+
+// y[..., :] = weight[ids[...]]
+static Tensor embedding_fwd(const Tensor &ids, const Tensor &weight) {
+  check_embed_table(weight, weight, "weight");
+  check_embed_idx(ids, ids, weight, "ids");
+  const HIPDeviceGuard guard(weight.device());
+  const int64_t N = weight.size(1);
+  Tensor y = at::empty(embed_out_shape(ids, N), weight.options());
+  CHK(embed_gather(weight.data_ptr(), ids.data_ptr(),
+                   ids.scalar_type() == at::kLong, y.data_ptr(), ids.numel(),
+                   (int)N, weight.size(0), cur_stream()));
+  return y;
+}
+
+// y = dropout(LN(tok[ids] + pos[position] (+ typ[type_ids]))); position is
+// position_ids or, without them, the index along ids' last dimension.
+// Returns {y, sum, mean, rstd} and, when p > 0, the keep mask [numel/8].
+static std::vector<Tensor> embed_ln_fwd_b(
+    const Tensor &ids, const Tensor &tok, const Tensor &pos,
+    const c10::optional<Tensor> &typ, const c10::optional<Tensor> &type_ids,
+    const c10::optional<Tensor> &position_ids, const Tensor &gamma,
+    const Tensor &beta, double eps, const c10::optional<Tensor> &state,
+    double p, int64_t site) {
+  check_embed_table(tok, tok, "tok_w");
+  check_embed_table(pos, tok, "pos_w");
+  check_embed_idx(ids, ids, tok, "ids");
+  TORCH_CHECK(ids.dim() >= 1, "ids must have a sequence dimension");
+  TORCH_CHECK(typ.has_value() == type_ids.has_value(),
+              "typ_w and type_ids are given together or not at all");
+  if (typ) {
+    check_embed_table(*typ, tok, "typ_w");
+    check_embed_idx(*type_ids, ids, tok, "type_ids");
+  }
+  if (position_ids) check_embed_idx(*position_ids, ids, tok, "position_ids");
+  const int64_t N = tok.size(1), M = ids.numel(), S = ids.size(-1);
+  TORCH_CHECK(N <= 2048, "embed_ln_fwd: N must be at most 2048, got ", N);
+  TORCH_CHECK(position_ids || S <= pos.size(0), "sequence length ", S,
+              " exceeds the position table's ", pos.size(0), " rows");
+  check_ln_vec(gamma, N, tok, "gamma");
+  check_ln_vec(beta, N, tok, "beta");
+  const bool drop = p > 0;
+  DropParams d = {0, 0, 1.f};
+  if (drop) {
+    TORCH_CHECK(state.has_value(), "embed_ln_fwd: p > 0 needs the rng state");
+    check_rng_state(*state, tok);
+    d = check_drop_params(p, site);
+    TORCH_CHECK(dropout_numel_ok(M * N), "embed_ln_fwd: output too large");
+  }
+  const HIPDeviceGuard guard(tok.device());
+  auto f32 = tok.options().dtype(at::kFloat);
+  Tensor y = at::empty(embed_out_shape(ids, N), tok.options());
+  Tensor sum = at::empty({M, N}, tok.options());
+  Tensor mean = at::empty({M}, f32), rstd = at::empty({M}, f32);
+  Tensor mask;
+  if (drop) mask = at::empty({M * N / 8}, tok.options().dtype(at::kByte));
+  CHK(embed_ln_fwd(
+      tok.data_ptr(), pos.data_ptr(), typ ? typ->data_ptr() : nullptr,
+      ids.data_ptr(), position_ids ? position_ids->data_ptr() : nullptr,
+      type_ids ? type_ids->data_ptr() : nullptr,
+      ids.scalar_type() == at::kLong, gamma.data_ptr<float>(),
+      beta.data_ptr<float>(), drop ? state->data_ptr<int64_t>() : nullptr,
+      d.site, d.thr, d.scale, sum.data_ptr(), y.data_ptr(),
+      mean.data_ptr<float>(), rstd.data_ptr<float>(),
+      drop ? mask.data_ptr<uint8_t>() : nullptr, M, (int)S, (int)N,
+      tok.size(0), pos.size(0), typ ? typ->size(0) : 0, (float)eps,
+      cur_stream()));
+  if (drop) return {y, sum, mean, rstd, mask};
+  return {y, sum, mean, rstd};
+}
+
+// dW [rows][N]: dW[v] = sum of the dsum rows whose index is v. sorted_idx
+// and perm are torch.sort(idx.flatten(), stable=True); without them the
+// indices are the default positions of a [B][S] batch (dsum has B * S rows).
+static Tensor embedding_bwd(const Tensor &dsum,
+                            const c10::optional<Tensor> &sorted_idx,
+                            const c10::optional<Tensor> &perm, int64_t B,
+                            int64_t S, int64_t rows) {
+  TORCH_CHECK(dsum.is_cuda() && dsum.scalar_type() == at::kBFloat16 &&
+                  dsum.is_contiguous() && dsum.dim() == 2 &&
+                  dsum.size(0) >= 1,
+              "dsum must be a contiguous bf16 [n][N] GPU tensor");
+  const int64_t n = dsum.size(0), N = dsum.size(1);
+  TORCH_CHECK(N % 8 == 0 && N >= 8, "embedding_bwd: N must be a positive "
+              "multiple of 8, got ", N);
+  TORCH_CHECK(rows >= 1, "embedding_bwd: the table has no rows");
+  TORCH_CHECK(sorted_idx.has_value() == perm.has_value(),
+              "sorted_idx and perm are given together or not at all");
+  if (sorted_idx) {
+    for (const Tensor *t : {&*sorted_idx, &*perm})
+      TORCH_CHECK(t->is_cuda() && t->device() == dsum.device() &&
+                      t->scalar_type() == at::kLong && t->is_contiguous() &&
+                      t->dim() == 1 && t->numel() == n,
+                  "sorted_idx and perm must be contiguous int64 [", n,
+                  "] tensors on dsum's GPU");
+  } else {
+    TORCH_CHECK(B >= 1 && S >= 1 && B * S == n && S <= rows &&
+                    n <= (int64_t)INT32_MAX,
+                "embedding_bwd: default positions need B * S == ", n,
+                " and S <= rows, got B=", B, " S=", S, " rows=", rows);
+  }
+  const HIPDeviceGuard guard(dsum.device());
+  Tensor dW = at::empty({rows, N}, dsum.options());
+  Tensor slab = at::empty({embed_bwd_chunks(n), 2, N},
+                          dsum.options().dtype(at::kFloat));
+  CHK(embed_bwd(sorted_idx ? sorted_idx->data_ptr<int64_t>() : nullptr,
+                perm ? perm->data_ptr<int64_t>() : nullptr, (int)B, (int)S,
+                dsum.data_ptr(), dW.data_ptr(), slab.data_ptr<float>(), n,
+                (int)N, rows, cur_stream()));
+  return dW;
+}
+
 // ------------------------- linear -------------------------
 static Tensor linear_fwd(const Tensor &x, const Tensor &w, const Tensor &b) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16);
@@ -1968,6 +2110,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_drop_add_bwd", &layernorm_drop_add_bwd, py::arg("dy"),
         py::arg("s"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
         py::arg("mask"), py::arg("p"));
+  m.attr("EMBED_BWD_CHUNK") = EMBED_BWD_CHUNK;
+  m.def("embedding_fwd", &embedding_fwd, py::arg("ids"), py::arg("weight"));
+  m.def("embed_ln_fwd", &embed_ln_fwd_b, py::arg("ids"), py::arg("tok_w"),
+        py::arg("pos_w"), py::arg("typ_w"), py::arg("type_ids"),
+        py::arg("position_ids"), py::arg("gamma"), py::arg("beta"),
+        py::arg("eps"), py::arg("state"), py::arg("p"), py::arg("site"));
+  m.def("embedding_bwd", &embedding_bwd, py::arg("dsum"),
+        py::arg("sorted_idx"), py::arg("perm"), py::arg("B"), py::arg("S"),
+        py::arg("rows"));
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_bwd", &linear_bwd);
   m.def("linear_dgrad", &linear_dgrad);

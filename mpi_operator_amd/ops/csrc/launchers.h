@@ -29,6 +29,13 @@ struct OptDesc {
   long numel;
 };
 
+// Sorted-index entries per workgroup of the embedding table-gradient kernels
+// (embedding.hip); sizes their fp32 slab, [ceil(n / chunk)][2][N].
+constexpr int EMBED_BWD_CHUNK = 32;
+static inline long embed_bwd_chunks(long n) {
+  return (n + EMBED_BWD_CHUNK - 1) / EMBED_BWD_CHUNK;
+}
+
 extern "C" {
 
 // ---- elementwise.hip ----
@@ -315,6 +322,29 @@ hipError_t dropout_fwd(const void *x, const int64_t *state, uint32_t site,
                        long n, hipStream_t s);
 hipError_t dropout_bwd(const void *dy, const uint8_t *mask, float scale,
                        void *dx, long n, hipStream_t s);
+
+// ---- embedding.hip ----
+// indices are int32 or int64 (idx64), clamped into their table on the device
+hipError_t embed_gather(const void *weight, const void *ids, int idx64,
+                        void *y, long M, int N, long rows, hipStream_t s);
+// y = dropout(LN(tok[ids] + pos[position] (+ typ[type]))) over M = B * S
+// rows; sum_out is the bf16 sum ln_bwd reads as x. pos_ids == nullptr:
+// position = row % S. typ and typ_ids are both given or both nullptr.
+// mask == nullptr: no dropout (state, site, thr, scale unused).
+hipError_t embed_ln_fwd(const void *tok, const void *pos, const void *typ,
+                        const void *ids, const void *pos_ids,
+                        const void *typ_ids, int idx64, const float *gamma,
+                        const float *beta, const int64_t *state, uint32_t site,
+                        uint32_t thr, float scale, void *sum_out, void *y,
+                        float *mean, float *rstd, uint8_t *mask, long M, int S,
+                        int N, long V, long P, long TY, float eps,
+                        hipStream_t s);
+// dW[v] = sum of dsum rows with index v, from the stable sort (sorted_idx,
+// perm) of the n indices, or from the default-position closed form of a
+// [B][S] batch when both are nullptr; slab: [embed_bwd_chunks(n)][2][N] fp32
+hipError_t embed_bwd(const int64_t *sorted_idx, const int64_t *perm, int B,
+                     int S, const void *dsum, void *dW, float *slab, long n,
+                     int N, long rows, hipStream_t s);
 
 // ---- optimizer.hip ----
 int optim_block_count(const OptDesc *descs, int nt);

@@ -925,3 +925,142 @@ def layer_norm_drop_add(a, b, weight, bias, eps: float = 1e-12, p: float = 0.0,
         return layer_norm_add(a, b, weight, bias, eps)
     return layer_norm_drop_add_with_mask(a, b, weight, bias, eps, p, rng,
                                          site)[0]
+
+
+def __getattr__(name):
+    # Fx.EMBED_BWD_CHUNK: sorted-index entries per workgroup of the
+    # table-gradient kernels, csrc/launchers.h's constant read from the built
+    # extension. Runs of equal indices that cross a multiple of it take the
+    # two-level path through the fp32 slab.
+    if name == "EMBED_BWD_CHUNK":
+        return hip_ext().EMBED_BWD_CHUNK
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def _embed_table_grad(dsum, idx, rows: int):
+    """dW [rows, N] = per-row sums of dsum [T, N] over equal idx, on the
+    deterministic HIP kernels. The stable sort brings equal indices together
+    in ascending row order; it reads nothing on the host (capturable)."""
+    sorted_idx, perm = torch.sort(idx.reshape(-1).to(torch.int64), stable=True)
+    return hip_ext().embedding_bwd(dsum, sorted_idx, perm, 0, 0, rows)
+
+
+def _check_embed_table(w, name, like=None):
+    if w.dtype != torch.bfloat16 or w.dim() != 2 or not w.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous bf16 [rows, hidden] "
+                         f"table, got {w.dtype} {tuple(w.shape)}")
+    if like is not None and w.shape[1] != like.shape[1]:
+        raise ValueError(f"{name} has width {w.shape[1]}, the token table "
+                         f"{like.shape[1]}")
+
+
+class EmbeddingFn(torch.autograd.Function):
+    """weight[ids] for a bf16 table (csrc/embedding.hip): a HIP gather and a
+    bit-reproducible, atomics-free table gradient."""
+
+    @staticmethod
+    def forward(ctx, ids, weight):
+        ctx.save_for_backward(ids)
+        ctx.rows = weight.shape[0]
+        return hip_ext().embedding_fwd(ids, weight)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (ids,) = ctx.saved_tensors
+        d2 = dy.contiguous().view(-1, dy.shape[-1])
+        return None, _embed_table_grad(d2, ids, ctx.rows)
+
+
+def embedding(ids, weight):
+    """weight[ids] → bf16 [*ids.shape, hidden]; ids int32/int64, weight a
+    contiguous bf16 [rows, hidden] GPU table with hidden % 8 == 0. Indices
+    outside [0, rows) are clamped, not reported."""
+    _check_embed_table(weight, "weight")
+    return EmbeddingFn.apply(ids.contiguous(), weight)
+
+
+class EmbedLayerNormFn(torch.autograd.Function):
+    """dropout(LN(tok[ids] + pos[position] + typ[type])) in one kernel; the
+    backward reuses dropout_bwd and layernorm_bwd for dsum and scatters it
+    into the three tables with the sorted-run kernels. Returns (y, mask);
+    mask is None when p == 0."""
+
+    @staticmethod
+    def forward(ctx, ids, tok_w, pos_w, typ_w, ln_w, ln_b, eps, type_ids,
+                position_ids, p, state, site):
+        out = hip_ext().embed_ln_fwd(ids, tok_w, pos_w, typ_w, type_ids,
+                                     position_ids, ln_w, ln_b, eps, state, p,
+                                     site)
+        y, s, mean, rstd = out[:4]
+        mask = out[4] if p > 0 else None
+        ctx.save_for_backward(s, ln_w, mean, rstd, mask, ids, type_ids,
+                              position_ids)
+        ctx.p = p
+        ctx.rows = (tok_w.shape[0], pos_w.shape[0],
+                    typ_w.shape[0] if typ_w is not None else 0)
+        if mask is not None:
+            ctx.mark_non_differentiable(mask)
+        ctx.set_materialize_grads(False)
+        return y, mask
+
+    @staticmethod
+    def backward(ctx, dy, _dmask=None):
+        s, ln_w, mean, rstd, mask, ids, type_ids, position_ids = \
+            ctx.saved_tensors
+        ext = hip_ext()
+        d = dy.contiguous()
+        if mask is not None:
+            d = ext.dropout_bwd(d.view(-1), mask, ctx.p)
+        dsum, dg, db = ext.layernorm_bwd(d.view(s.shape), s, ln_w, mean, rstd)
+        v, npos, ntyp = ctx.rows
+        dtok = _embed_table_grad(dsum, ids, v)
+        if position_ids is None:
+            # sorted order known in closed form: position-major, batch ascending
+            seq = ids.shape[-1]
+            dpos = ext.embedding_bwd(dsum, None, None, ids.numel() // seq,
+                                     seq, npos)
+        else:
+            dpos = _embed_table_grad(dsum, position_ids, npos)
+        dtyp = (_embed_table_grad(dsum, type_ids, ntyp)
+                if type_ids is not None else None)
+        return (None, dtok, dpos, dtyp, dg, db) + (None,) * 6
+
+
+def embed_layer_norm_with_mask(ids, tok_w, pos_w, typ_w, ln_w, ln_b,
+                               eps: float = 1e-12, type_ids=None,
+                               position_ids=None, p: float = 0.0, rng=None,
+                               site: int = 0):
+    """(y, mask) of EmbedLayerNormFn; mask is the uint8 keep bitmask
+    [numel/8] of Fx.dropout at the same (rng, site), None when p == 0."""
+    _check_p(p)
+    if p > 0 and rng is None:
+        raise ValueError("embed_layer_norm: p > 0 needs a DropoutRng")
+    _check_embed_table(tok_w, "tok_w")
+    _check_embed_table(pos_w, "pos_w", tok_w)
+    if type_ids is not None:
+        _check_embed_table(typ_w, "typ_w", tok_w)
+    for name, t in (("type_ids", type_ids), ("position_ids", position_ids)):
+        if t is not None and (t.shape != ids.shape or t.dtype != ids.dtype):
+            raise ValueError(f"{name} must have ids' shape and dtype, got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    cont = lambda t: None if t is None else t.contiguous()
+    return EmbedLayerNormFn.apply(
+        ids.contiguous(), tok_w, pos_w, typ_w if type_ids is not None else None,
+        ln_w, ln_b, eps, cont(type_ids), cont(position_ids), p,
+        rng.state if p > 0 else None, site)
+
+
+def embed_layer_norm(ids, tok_w, pos_w, typ_w, ln_w, ln_b, eps: float = 1e-12,
+                     type_ids=None, position_ids=None, p: float = 0.0,
+                     rng=None, site: int = 0):
+    """The BERT embedding block on csrc/embedding.hip: y = dropout(LN(
+    tok_w[ids] + pos_w[position] + typ_w[type_ids])) → bf16 [*ids.shape,
+    hidden]. position is position_ids or, by default, the index along ids'
+    last dimension; without type_ids the type table is left out and gets no
+    gradient. Tables are contiguous bf16 of equal width (hidden % 8 == 0,
+    hidden <= 2048), ln_w / ln_b fp32. The three table rows are added in fp32
+    and rounded once. Dropout draws Fx.dropout's mask for the same (rng,
+    site). Indices outside their table are clamped, not reported."""
+    return embed_layer_norm_with_mask(ids, tok_w, pos_w, typ_w, ln_w, ln_b,
+                                      eps, type_ids, position_ids, p, rng,
+                                      site)[0]

@@ -474,3 +474,60 @@ def varlen_attn_dropout_keep(seed: int, offset: int, site: int, cu_seqlens,
     dense = attn_dropout_keep(seed, offset, site, N, H, max_seqlen, p)
     return [dense[n, :, :L, :L].clone() if L else None
             for n, L in enumerate(lens)]
+
+
+# -------------------------------------------------------------- embeddings
+def embedding_bwd(dy, idx, rows: int):
+    """Specification of the table-gradient kernels: dW [rows, N] with
+    dW[v] = Σ_{i: idx[i] = v} dy[i], rows no index names zero. dy
+    [*idx.shape, N]; computed in dy's dtype (fp64 in the tests)."""
+    d2 = dy.reshape(-1, dy.shape[-1])
+    return torch.zeros(rows, d2.shape[1], dtype=dy.dtype,
+                       device=dy.device).index_add_(0, idx.reshape(-1).long(), d2)
+
+
+def _embed_positions(ids, position_ids):
+    if position_ids is not None:
+        return position_ids.long()
+    return torch.arange(ids.shape[-1], device=ids.device).expand(ids.shape)
+
+
+def embed_layer_norm_fwd(ids, tok_w, pos_w, typ_w, ln_w, ln_b, eps: float,
+                         type_ids=None, position_ids=None, keep=None,
+                         drop_scale: float = 1.0, sum_dtype=None):
+    """Specification of embed_ln_fwd_k, in the tables' dtype: s = tok_w[ids]
+    + pos_w[position] (+ typ_w[type_ids]) rounded ONCE through sum_dtype
+    (torch.bfloat16 for the kernel, None = no rounding), statistics and xhat
+    from that rounded s, y = LN(s)·keep·drop_scale. keep: bool of y's shape
+    or None. Returns (y, s, mean, rstd)."""
+    s = tok_w[ids.long()] + pos_w[_embed_positions(ids, position_ids)]
+    if type_ids is not None:
+        s = s + typ_w[type_ids.long()]
+    if sum_dtype is not None:
+        s = s.to(sum_dtype).to(tok_w.dtype)
+    mean = s.mean(-1, keepdim=True)
+    rstd = torch.rsqrt(((s - mean) ** 2).mean(-1, keepdim=True) + eps)
+    y = (s - mean) * rstd * ln_w + ln_b
+    if keep is not None:
+        y = y * keep.to(y.dtype) * drop_scale
+    return y, s, mean.squeeze(-1), rstd.squeeze(-1)
+
+
+def embed_layer_norm_bwd(dy, ids, s, mean, rstd, ln_w, rows, type_ids=None,
+                         position_ids=None, keep=None, drop_scale: float = 1.0):
+    """Backward of embed_layer_norm_fwd from its saved (s, mean, rstd); rows
+    = (tok, pos, typ) table row counts. Returns (dsum, dtok, dpos, dtyp,
+    dln_w, dln_b); dtyp is None without type_ids."""
+    if keep is not None:
+        dy = dy * keep.to(dy.dtype) * drop_scale
+    xhat = (s - mean.unsqueeze(-1)) * rstd.unsqueeze(-1)
+    red = tuple(range(dy.dim() - 1))
+    dln_w, dln_b = (dy * xhat).sum(red), dy.sum(red)
+    g = dy * ln_w
+    dsum = rstd.unsqueeze(-1) * (g - g.mean(-1, keepdim=True)
+                                 - xhat * (g * xhat).mean(-1, keepdim=True))
+    dtok = embedding_bwd(dsum, ids, rows[0])
+    dpos = embedding_bwd(dsum, _embed_positions(ids, position_ids), rows[1])
+    dtyp = (embedding_bwd(dsum, type_ids, rows[2])
+            if type_ids is not None else None)
+    return dsum, dtok, dpos, dtyp, dln_w, dln_b
