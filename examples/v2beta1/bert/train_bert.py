@@ -24,26 +24,37 @@ from mpi_operator_amd.models.bert import (bert_large, bert_base, bert_param_grou
 from mpi_operator_amd.optim import FusedAdamW, FusedLAMB, FusedSGD
 
 
-def synthetic_batch(batch, seq, vocab, device):
+def synthetic_batch(batch, seq, vocab, device, max_predictions=None):
     ids = torch.randint(0, vocab, (batch, seq), device=device)
     type_ids = torch.zeros_like(ids)
     mlm_labels = torch.full_like(ids, -100)
     mask = torch.rand(batch, seq, device=device) < 0.15
+    if max_predictions is not None:
+        # at most max_predictions labels per sequence, as a real data
+        # pipeline emits them: the surplus, highest positions first, is
+        # unlabelled (same random draws as without the cap)
+        mask &= mask.cumsum(1) <= max_predictions
     mlm_labels[mask] = ids[mask]
     nsp = torch.randint(0, 2, (batch,), device=device)
     return ids, type_ids, mlm_labels, nsp
 
 
-def ragged_batches(n, batch, seq, min_len, vocab, device, seed, packed, max_seq):
+def ragged_batches(n, batch, seq, min_len, vocab, device, seed, packed, max_seq,
+                   max_predictions=None):
     """n ragged batches as (model args, model kwargs, real tokens), built
     ahead of the timed loop the way a data pipeline runs ahead of the step
     (pack_padded_batch reads the lengths on the host). The lengths come from
     a seeded CPU generator, so `padded` and `packed` see the same ones."""
     g = torch.Generator().manual_seed(seed)
     out = []
+    # the MLM head's row capacity: sequence slots (= batch, padded or packed)
+    # times the per-sequence cap
+    head = {} if max_predictions is None else {
+        "max_predictions": batch * max_predictions}
     for _ in range(n):
         lens = torch.randint(min_len, seq + 1, (batch,), generator=g)
-        ids, type_ids, mlm_labels, nsp = synthetic_batch(batch, seq, vocab, device)
+        ids, type_ids, mlm_labels, nsp = synthetic_batch(batch, seq, vocab, device,
+                                                         max_predictions)
         mask = (torch.arange(seq)[None] < lens[:, None]).to(device)
         mlm_labels = torch.where(mask, mlm_labels, torch.full_like(mlm_labels, -100))
         if packed:
@@ -53,9 +64,10 @@ def ragged_batches(n, batch, seq, min_len, vocab, device, seed, packed, max_seq)
             # max_seqlen = seq, not this batch's longest: every step has one shape
             out.append(((pk.ids, pk.type_ids, None, pk.mlm_labels, nsp),
                         dict(cu_seqlens=pk.cu_seqlens, max_seqlen=seq,
-                             position_ids=pk.position_ids), int(lens.sum())))
+                             position_ids=pk.position_ids, **head),
+                        int(lens.sum())))
         else:
-            out.append(((ids, type_ids, mask.long(), mlm_labels, nsp), {},
+            out.append(((ids, type_ids, mask.long(), mlm_labels, nsp), dict(head),
                         int(lens.sum())))
     return out
 
@@ -80,9 +92,15 @@ def main():
                          "mask, or packed without padding (cu_seqlens)")
     ap.add_argument("--min-len", type=int, default=64,
                     help="--varlen: lengths are uniform in [min-len, seq]")
+    ap.add_argument("--max-predictions", type=int, default=None,
+                    help="run the MLM head on the labelled positions only, at "
+                         "most this many per sequence (public recipes: 20 at "
+                         "seq 128, 76-80 at seq 512); default: on all rows")
     args = ap.parse_args()
     if args.varlen != "off" and not 1 <= args.min_len <= args.seq:
         ap.error("--min-len must be in [1, --seq]")
+    if args.max_predictions is not None and args.max_predictions < 1:
+        ap.error("--max-predictions must be at least 1")
 
     hvd.init()
     use_cuda = torch.cuda.is_available()
@@ -116,11 +134,25 @@ def main():
         opt.step()
         return loss
 
+    dropped = []  # device counters of labelled rows past the head's capacity
+    if args.max_predictions is not None:
+        def step():  # noqa: F811 — labels-in-forward on the labelled rows
+            ids, type_ids, mlm_labels, nsp = synthetic_batch(
+                args.batch, args.seq, vocab, device, args.max_predictions)
+            opt.zero_grad()
+            loss = model(ids, type_ids, None, mlm_labels, nsp,
+                         max_predictions=args.batch * args.max_predictions)
+            dropped.append(model.mlm_counts[1])
+            loss.backward()
+            opt.step()
+            return loss
+
     real_tokens = 0
     if args.varlen != "off":
         batches = ragged_batches(args.warmup + args.steps, args.batch, args.seq,
                                  args.min_len, vocab, device, args.seed,
-                                 args.varlen == "packed", model.cfg.max_seq)
+                                 args.varlen == "packed", model.cfg.max_seq,
+                                 args.max_predictions)
         real_tokens = sum(b[2] for b in batches[args.warmup:])
         feed = iter(batches)
 
@@ -128,6 +160,8 @@ def main():
             a, kw, _ = next(feed)
             opt.zero_grad()
             loss = model(*a, **kw)
+            if "max_predictions" in kw:
+                dropped.append(model.mlm_counts[1])
             loss.backward()
             opt.step()
             return loss
@@ -155,6 +189,13 @@ def main():
             print(f"bert varlen={args.varlen}: {tok:.0f} real tokens/sec "
                   f"(rank 0's lengths; {share:.1%} of batch*seq is padding)",
                   flush=True)
+        if dropped:
+            # the one host read of the counters, after the timed loop; the
+            # synthetic batches respect the cap, so nothing may be dropped
+            n = int(torch.stack(dropped).sum())
+            print(f"bert max_predictions={args.max_predictions}: dropped = {n} "
+                  f"labelled rows over {len(dropped)} steps", flush=True)
+            assert n == 0, "labelled rows exceeded the MLM head's capacity"
 
 
 if __name__ == "__main__":

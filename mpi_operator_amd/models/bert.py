@@ -433,6 +433,9 @@ class BertForPreTraining(nn.Module):
         # decoder tied to token embeddings (standard BERT weight tying)
         self.mlm_bias = nn.Parameter(torch.zeros(cfg.vocab_size))
         self.nsp = BertLinear(cfg.hidden, 2)
+        # int32 {selected, dropped} of the last forward with max_predictions;
+        # a plain attribute (no state_dict entry), read by the caller
+        self.mlm_counts = None
 
     def seed_dropout(self, seed: int):
         """BertModel.seed_dropout of the trunk."""
@@ -449,14 +452,41 @@ class BertForPreTraining(nn.Module):
 
     def forward(self, ids, type_ids=None, attn_mask=None, mlm_labels=None,
                 nsp_labels=None, *, cu_seqlens=None, max_seqlen=None,
-                position_ids=None):
+                position_ids=None, max_predictions: Optional[int] = None):
         """cu_seqlens, max_seqlen, position_ids: a packed batch, as in
         BertModel.forward. mlm_labels is then [1, T] with −100 at the unused
         tail, nsp_labels / nsp_logits have one entry per sequence slot, and
-        an empty slot's nsp label is −100."""
+        an empty slot's nsp label is −100.
+
+        max_predictions (host int, with mlm_labels): run the MLM head on the
+        labelled rows only, at most max_predictions of them for the whole
+        call (batch · max_predictions_per_seq of the public recipes; a packed
+        batch: its sequence slots · that). The rows are selected on the
+        device (Fx.mlm_select), so the shapes depend on max_predictions
+        alone and the step stays capturable. The loss is still the sum over
+        the selected rows / their number: the default path's loss up to
+        rounding as long as no more rows are labelled than fit. Labelled
+        rows past the capacity are dropped, last rows first;
+        self.mlm_counts (int32 {selected, dropped}, on the device) tells
+        after the step. Any capacity >= 1 works: no route of the head needs
+        it aligned."""
+        if max_predictions is not None:
+            if mlm_labels is None:
+                raise ValueError("max_predictions selects rows by mlm_labels; "
+                                 "the logits path has none")
+            if max_predictions < 1:
+                raise ValueError(f"max_predictions must be at least 1, got "
+                                 f"{max_predictions}")
         x = self.bert(ids, type_ids, attn_mask, cu_seqlens=cu_seqlens,
                       max_seqlen=max_seqlen, position_ids=position_ids)
-        h = self.mlm_ln(F.gelu(self.mlm_transform(x), approximate="tanh"))
+        if max_predictions is not None:
+            pos, slot, mlm_labels, self.mlm_counts = Fx.mlm_select(
+                mlm_labels, int(max_predictions))
+            # NSP below still reads x: autograd sums the two gradients
+            h = Fx.gather_rows(x.reshape(-1, x.shape[-1]), pos, slot)[None]
+        else:
+            h = x
+        h = self.mlm_ln(F.gelu(self.mlm_transform(h), approximate="tanh"))
         tok_w = self.bert.embeddings.tok.weight
         if mlm_labels is not None:
             # labels-in-forward (HF-style) training path: the fused MLM head

@@ -1067,6 +1067,70 @@ static Tensor embedding_bwd(const Tensor &dsum,
   return dW;
 }
 
+// --------------- MLM head on the labelled rows (mlm_select.hip) ---------------
+// {pos [P], slot [M], labels_c [P], counts [2]} of the rows with
+// labels != ignore_index, the first `capacity` of them in row order
+static std::vector<Tensor> mlm_select(const Tensor &labels, int64_t capacity,
+                                      int64_t ignore_index) {
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong &&
+                  labels.is_contiguous() && labels.dim() == 1 &&
+                  labels.numel() >= 1,
+              "labels must be a non-empty contiguous int64 [M] GPU tensor");
+  const int64_t M = labels.numel();
+  TORCH_CHECK(M <= (int64_t)INT32_MAX, "mlm_select: too many rows, ", M);
+  TORCH_CHECK(capacity >= 1 && capacity <= (int64_t)INT32_MAX,
+              "mlm_select: capacity must be at least 1, got ", capacity);
+  const HIPDeviceGuard guard(labels.device());
+  auto i32 = labels.options().dtype(at::kInt);
+  Tensor pos = at::empty({capacity}, i32), slot = at::empty({M}, i32);
+  Tensor labels_c = at::empty({capacity}, labels.options());
+  Tensor counts = at::empty({2}, i32);
+  CHK(mlm_select_launch(labels.data_ptr<int64_t>(), ignore_index,
+                        pos.data_ptr<int>(), slot.data_ptr<int>(),
+                        labels_c.data_ptr<int64_t>(), counts.data_ptr<int>(), M,
+                        (int)capacity, cur_stream()));
+  return {pos, slot, labels_c, counts};
+}
+
+static void check_rows(const Tensor &src, const Tensor &map, const char *sname,
+                       const char *mname) {
+  TORCH_CHECK(src.is_cuda() && src.scalar_type() == at::kBFloat16 &&
+                  src.is_contiguous() && src.dim() == 2 && src.size(0) >= 1,
+              sname, " must be a contiguous bf16 [rows][hidden] GPU tensor");
+  TORCH_CHECK(src.size(1) % 8 == 0 && src.size(1) >= 8 &&
+                  src.size(1) <= (int64_t)INT32_MAX,
+              sname, ": hidden must be a positive multiple of 8, got ",
+              src.size(1));
+  TORCH_CHECK(src.size(0) <= (int64_t)INT32_MAX, sname, ": too many rows");
+  TORCH_CHECK(map.is_cuda() && map.device() == src.device() &&
+                  map.scalar_type() == at::kInt && map.is_contiguous() &&
+                  map.dim() == 1 && map.numel() >= 1,
+              mname, " must be a non-empty contiguous int32 vector on ", sname,
+              "'s GPU");
+}
+
+// out [P][hidden]: out[k] = x[pos[k]], zeros where pos[k] < 0
+static Tensor gather_rows_fwd(const Tensor &x, const Tensor &pos) {
+  check_rows(x, pos, "x", "pos");
+  const HIPDeviceGuard guard(x.device());
+  Tensor out = at::empty({pos.numel(), x.size(1)}, x.options());
+  CHK(gather_rows_launch(x.data_ptr(), pos.data_ptr<int>(), out.data_ptr(),
+                         pos.numel(), x.size(0), (int)x.size(1),
+                         cur_stream()));
+  return out;
+}
+
+// dx [M][hidden]: dx[r] = dout[slot[r]], zeros where slot[r] < 0
+static Tensor gather_rows_bwd(const Tensor &dout, const Tensor &slot) {
+  check_rows(dout, slot, "dout", "slot");
+  const HIPDeviceGuard guard(dout.device());
+  Tensor dx = at::empty({slot.numel(), dout.size(1)}, dout.options());
+  CHK(scatter_rows_launch(dout.data_ptr(), slot.data_ptr<int>(),
+                          dx.data_ptr(), slot.numel(), dout.size(0),
+                          (int)dout.size(1), cur_stream()));
+  return dx;
+}
+
 // ------------------------- linear -------------------------
 static Tensor linear_fwd(const Tensor &x, const Tensor &w, const Tensor &b) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16);
@@ -2119,6 +2183,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("embedding_bwd", &embedding_bwd, py::arg("dsum"),
         py::arg("sorted_idx"), py::arg("perm"), py::arg("B"), py::arg("S"),
         py::arg("rows"));
+  m.attr("MLM_SELECT_TILE") = MLM_SELECT_TILE;
+  m.def("mlm_select", &mlm_select, py::arg("labels"), py::arg("capacity"),
+        py::arg("ignore_index"));
+  m.def("gather_rows_fwd", &gather_rows_fwd, py::arg("x"), py::arg("pos"));
+  m.def("gather_rows_bwd", &gather_rows_bwd, py::arg("dout"), py::arg("slot"));
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_bwd", &linear_bwd);
   m.def("linear_dgrad", &linear_dgrad);

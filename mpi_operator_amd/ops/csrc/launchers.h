@@ -36,6 +36,11 @@ static inline long embed_bwd_chunks(long n) {
   return (n + EMBED_BWD_CHUNK - 1) / EMBED_BWD_CHUNK;
 }
 
+// Labels per loop iteration of the one-workgroup select kernel
+// (mlm_select.hip): M one short of, at and past a multiple of it are the
+// edges its tests probe.
+constexpr int MLM_SELECT_TILE = 2048;
+
 extern "C" {
 
 // ---- elementwise.hip ----
@@ -345,6 +350,24 @@ hipError_t embed_ln_fwd(const void *tok, const void *pos, const void *typ,
 hipError_t embed_bwd(const int64_t *sorted_idx, const int64_t *perm, int B,
                      int S, const void *dsum, void *dW, float *slab, long n,
                      int N, long rows, hipStream_t s);
+
+// ---- mlm_select.hip ----
+// Stable compaction of the rows with labels[r] != ignore_index, at most P of
+// them: pos [P] the row of slot k in ascending row order (-1 unused), slot
+// [M] the inverse (-1: unlabelled or past the capacity), labels_c [P] the
+// label of slot k (ignore_index unused), counts {selected, dropped}. Writes
+// every element of all four; labels and slot 8-byte aligned.
+hipError_t mlm_select_launch(const int64_t *labels, int64_t ignore_index,
+                             int *pos, int *slot, int64_t *labels_c,
+                             int *counts, long M, int P, hipStream_t s);
+// out [P][N] bf16: out[k] = x[pos[k]] of x [M][N], zeros where pos[k] is no
+// row of x; N % 8 == 0
+hipError_t gather_rows_launch(const void *x, const int *pos, void *out, long P,
+                              long M, int N, hipStream_t s);
+// dx [M][N] bf16: dx[r] = dout[slot[r]] of dout [P][N], zeros where slot[r]
+// is no row of dout; every row of dx is written once
+hipError_t scatter_rows_launch(const void *dout, const int *slot, void *dx,
+                               long M, long P, int N, hipStream_t s);
 
 // ---- optimizer.hip ----
 int optim_block_count(const OptDesc *descs, int nt);

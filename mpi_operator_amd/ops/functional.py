@@ -406,6 +406,61 @@ def mlm_head_loss(h, w, b, target, ignore_index=-100):
     return MlmHeadLossFn.apply(h, w, b, target, ignore_index)
 
 
+def mlm_select(labels, capacity: int, ignore_index: int = -100):
+    """The labelled rows of an MLM batch at a fixed capacity
+    (csrc/mlm_select.hip): labels int64, flattened to [M]. Returns
+    (pos, slot, labels_c, counts): pos int32 [capacity], the row of the k-th
+    labelled row in ascending order (-1 in unused slots); slot int32 [M], its
+    inverse (-1: unlabelled, or dropped because capacity rows came before
+    it); labels_c int64 [capacity] (ignore_index in unused slots); counts
+    int32 {selected, dropped}. Not differentiable. On the GPU nothing is read
+    on the host, so the call is capturable and the result is bit-identical
+    from call to call; the CPU reference synchronises."""
+    if capacity < 1:
+        raise ValueError(f"mlm_select: capacity must be at least 1, got "
+                         f"{capacity}")
+    if labels.dtype != torch.int64:
+        raise ValueError(f"mlm_select: labels must be int64, got "
+                         f"{labels.dtype}")
+    labels = labels.reshape(-1)
+    with torch.no_grad():
+        if labels.is_cuda:
+            return tuple(hip_ext().mlm_select(labels.contiguous(),
+                                              int(capacity), int(ignore_index)))
+        return ref.mlm_select(labels, int(capacity), int(ignore_index))
+
+
+class GatherRowsFn(torch.autograd.Function):
+    """out[k] = x2d[pos[k]] (zeros where pos[k] < 0); the backward writes
+    every row of dx once from the inverse map: dx[r] = dout[slot[r]] or
+    zeros. No atomics and no cleared buffer in either direction."""
+
+    @staticmethod
+    def forward(ctx, x2d, pos, slot):
+        ctx.save_for_backward(slot)
+        ctx.hip = x2d.is_cuda and x2d.dtype == torch.bfloat16
+        if ctx.hip:
+            return hip_ext().gather_rows_fwd(x2d.contiguous(), pos)
+        return ref.rows_by_map(x2d, pos)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (slot,) = ctx.saved_tensors
+        if ctx.hip:
+            return hip_ext().gather_rows_bwd(dout.contiguous(), slot), None, None
+        return ref.rows_by_map(dout, slot), None, None
+
+
+def gather_rows(x2d, pos, slot):
+    """x2d [M, hidden] → [capacity, hidden] at Fx.mlm_select's (pos, slot);
+    GPU bf16 (hidden % 8 == 0) runs csrc/mlm_select.hip."""
+    if x2d.dim() != 2 or slot.numel() != x2d.shape[0]:
+        raise ValueError(f"gather_rows: x2d must be [M, hidden] with one slot "
+                         f"entry per row, got {tuple(x2d.shape)} and "
+                         f"{slot.numel()} slots")
+    return GatherRowsFn.apply(x2d, pos, slot)
+
+
 class FfnFn(torch.autograd.Function):
     """BERT FFN pair fc2(gelu(fc1(x))) with the GELU fused into the GEMM
     epilogues on both sides: fc1's epilogue emits (gelu(h), gelu'(h)) off a
@@ -934,6 +989,9 @@ def __getattr__(name):
     # two-level path through the fp32 slab.
     if name == "EMBED_BWD_CHUNK":
         return hip_ext().EMBED_BWD_CHUNK
+    # Fx.MLM_SELECT_TILE: labels per loop iteration of the select kernel
+    if name == "MLM_SELECT_TILE":
+        return hip_ext().MLM_SELECT_TILE
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

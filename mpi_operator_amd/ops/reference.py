@@ -531,3 +531,33 @@ def embed_layer_norm_bwd(dy, ids, s, mean, rstd, ln_w, rows, type_ids=None,
     dtyp = (embedding_bwd(dsum, type_ids, rows[2])
             if type_ids is not None else None)
     return dsum, dtok, dpos, dtyp, dln_w, dln_b
+
+
+# ------------------------------------------------- MLM head on labelled rows
+def mlm_select(labels, capacity: int, ignore_index: int = -100):
+    """Specification of mlm_select_k: the rows r with labels[r] !=
+    ignore_index, the first `capacity` of them in ascending order. Returns
+    pos int32 [capacity] (-1 unused), slot int32 [M] (the slot of row r; -1
+    if unlabelled or past the capacity), labels_c int64 [capacity]
+    (ignore_index unused) and counts int32 {selected, dropped}. Reads the
+    count on the host (nonzero)."""
+    labels = labels.reshape(-1)
+    rows = torch.nonzero(labels != ignore_index).flatten()
+    sel = rows[:capacity]
+    n = sel.numel()
+    i32 = dict(dtype=torch.int32, device=labels.device)
+    pos = torch.full((capacity,), -1, **i32)
+    pos[:n] = sel.to(torch.int32)
+    slot = torch.full((labels.numel(),), -1, **i32)
+    slot[sel] = torch.arange(n, **i32)
+    labels_c = labels.new_full((capacity,), ignore_index)
+    labels_c[:n] = labels[sel]
+    counts = torch.tensor([n, rows.numel() - n], **i32)
+    return pos, slot, labels_c, counts
+
+
+def rows_by_map(src, index):
+    """out[r] = src[index[r]], zeros where index[r] < 0: gather_rows_k with
+    index = pos, scatter_rows_k (its backward) with index = slot."""
+    picked = src[index.clamp(min=0).long()]
+    return torch.where((index >= 0)[:, None], picked, torch.zeros_like(picked))
