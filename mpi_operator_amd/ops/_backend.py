@@ -33,6 +33,12 @@ def _try_load():
         # "0" keeps the one-element-per-lane stores (A/B lever)
         if os.environ.get("MPIAMD_EPI_VEC", "1") == "0":
             _ext.set_epilogue_vec(False)
+        # MPIAMD_PAIR_BWD (default "1"): a stride-1 conv's dgrad and wgrad
+        # GEMMs share one launch, wgrad workgroups first; "2" puts the dgrad
+        # workgroups first, "0" keeps the two launches (A/B levers)
+        pair = os.environ.get("MPIAMD_PAIR_BWD", "1")
+        if pair != "1":
+            _ext.set_pair_bwd(pair == "2", pair == "2")
         # MPIAMD_BN_PIPELINED (default "1"): software-pipelined BN statistics
         # producers; MPIAMD_BN_FINALIZE_COALESCED (default "1"): line-coalesced
         # BN finalize. "0" keeps the kernels they replace (A/B levers)

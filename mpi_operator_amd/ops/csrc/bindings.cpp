@@ -383,6 +383,152 @@ static std::vector<Tensor> conv2d_dgrad_bn(
   return {dx, slab};
 }
 
+// Both gradients of a stride-1 conv from one call: (dx, slab, dw), equal bit
+// for bit to conv2d_dgrad_bn (or, with want_bn false, conv2d_dgrad and an
+// empty slab) and conv2d_wgrad on the same inputs. x is the conv's input, so
+// dx has its shape. Same split counts and reduces; the two GEMMs share one
+// grid under set_pair_bwd. As for conv2d_dgrad_bn, an empty slab means the
+// caller runs bn_bwd.
+static std::vector<Tensor> conv_dgrad_wgrad_b(
+    const char *op, const Tensor &dy, const Tensor &w, const Tensor &x,
+    int64_t H, int64_t W, int64_t R, int64_t S, int64_t pad, bool want_bn,
+    const Tensor &bx, const Tensor &by, const Tensor &mean,
+    const Tensor &invstd, bool relu, const Tensor &mask) {
+  check_cl_bf16(dy, "dy");
+  check_cl_bf16(w, "w");
+  check_cl_bf16(x, "x");
+  check_same_device(w, dy, "w");
+  check_same_device(x, dy, "x");
+  TORCH_CHECK(x.size(2) == H && x.size(3) == W && w.size(2) == R &&
+                  w.size(3) == S, op, ": x is ", x.size(2), "x", x.size(3),
+              " and w ", w.size(2), "x", w.size(3), ", expected ", H, "x", W,
+              " and ", R, "x", S);
+  check_conv_geometry(op, true, x.size(0), x.size(1), H, W, w.size(0),
+                      w.size(1), R, S, dy.size(0), dy.size(1), dy.size(2),
+                      dy.size(3), 1, pad);
+  const HIPDeviceGuard guard(dy.device());
+  int N = dy.size(0), Kout = dy.size(1), HO = dy.size(2), WO = dy.size(3);
+  int C = w.size(1), RSC = (int)R * S * C;
+  long M = (long)N * H * W, Mo = (long)N * HO * WO;
+  auto f32 = dy.options().dtype(at::kFloat);
+  int dsplits = conv_splits(M, C, R * S * Kout);
+  int wsplits = wgrad_splits(Kout, RSC, Mo);
+  long rows = want_bn ? conv_dgrad_bn_rows(M, C, Kout, R, S, 1, dsplits) : 0;
+  Tensor dx = empty_cl_bf16(N, C, H, W, dy);
+  Tensor dw = at::empty({(int64_t)Kout, (int64_t)C, R, S},
+                        dy.options().dtype(at::kBFloat16),
+                        at::MemoryFormat::ChannelsLast);
+  Tensor wpartial = at::empty({(long)wsplits, (long)Kout, (long)RSC}, f32);
+  Tensor dpartial;
+  float *dp = nullptr;
+  if (dsplits > 1) {
+    dpartial = at::empty({(long)dsplits, M, (long)C}, f32);
+    dp = dpartial.data_ptr<float>();
+  }
+  if (rows == 0) {
+    CHK(conv_dgrad_wgrad(dy.data_ptr(), w.data_ptr(), x.data_ptr(),
+                         dx.data_ptr(), dw.data_ptr(), N, (int)H, (int)W, C,
+                         Kout, (int)R, (int)S, (int)pad, HO, WO, dsplits, dp,
+                         wsplits, wpartial.data_ptr<float>(), cur_stream()));
+    return {dx, at::empty({0}, f32), dw};
+  }
+  check_cl_bf16(bx, "bx");
+  TORCH_CHECK(bx.size(0) == N && bx.size(1) == C && bx.size(2) == H &&
+                  bx.size(3) == W, "bx must have the dgrad output's shape");
+  TORCH_CHECK(mean.numel() == C && invstd.numel() == C, "mean/invstd shape");
+  const uint8_t *mp = nullptr;
+  if (mask.defined() && mask.numel() > 0) {
+    TORCH_CHECK(mask.numel() == M * (C / 8), "mask shape");
+    mp = mask.data_ptr<uint8_t>();
+  }
+  if (relu && !mp) {
+    check_cl_bf16(by, "by");
+    TORCH_CHECK(by.numel() == bx.numel(), "by shape");
+  }
+  Tensor slab = at::empty({rows, 2, (long)C}, f32);
+  CHK(conv_dgrad_bn_wgrad(
+      dy.data_ptr(), w.data_ptr(), x.data_ptr(), dx.data_ptr(), dw.data_ptr(),
+      N, (int)H, (int)W, C, Kout, (int)R, (int)S, (int)pad, HO, WO, dsplits,
+      dp, wsplits, wpartial.data_ptr<float>(), bx.data_ptr(),
+      by.defined() && by.numel() > 0 ? by.data_ptr() : nullptr, mp,
+      mean.data_ptr<float>(), invstd.data_ptr<float>(), relu ? 1 : 0,
+      slab.data_ptr<float>(), cur_stream()));
+  return {dx, slab, dw};
+}
+
+static std::vector<Tensor> conv2d_dgrad_wgrad(const Tensor &dy, const Tensor &w,
+                                              const Tensor &x, int64_t H,
+                                              int64_t W, int64_t R, int64_t S,
+                                              int64_t pad) {
+  Tensor none;
+  auto r = conv_dgrad_wgrad_b("conv2d_dgrad_wgrad", dy, w, x, H, W, R, S, pad,
+                              false, none, none, none, none, false, none);
+  return {r[0], r[2]};
+}
+
+static std::vector<Tensor> conv2d_dgrad_bn_wgrad(
+    const Tensor &dy, const Tensor &w, const Tensor &x, int64_t H, int64_t W,
+    int64_t R, int64_t S, int64_t pad, const Tensor &bx, const Tensor &by,
+    const Tensor &mean, const Tensor &invstd, bool relu, const Tensor &mask) {
+  return conv_dgrad_wgrad_b("conv2d_dgrad_bn_wgrad", dy, w, x, H, W, R, S, pad,
+                            true, bx, by, mean, invstd, relu, mask);
+}
+
+// Test hook for the pair launcher (launchers.h pipe8_gemm_pair): two plain
+// GEMMs into the CALLER's outputs, unreduced, as one grid or as two launches.
+//   c1 [s1][M1][n1] fp32 = a1^T b1[:, :n1]   a1 [K1][M1], b1 [K1][ldb1]
+//   c2 [M2][n2] bf16 or [s2][M2][n2] fp32 = a2 b2[:, :n2]
+//                                             a2 [M2][K2], b2 [K2][ldb2]
+// The operands keep the kernels' 16-byte load granules whole (M1, K2, ldb1,
+// ldb2 multiples of 8, 16-byte aligned bases); n1, n2 and the outputs' base
+// addresses are free, and decide each problem's epilogue.
+static void pipe8_gemm_pair_b(const Tensor &a1, const Tensor &b1, Tensor c1,
+                              int64_t n1, const Tensor &a2, const Tensor &b2,
+                              Tensor c2, int64_t n2, bool paired,
+                              bool second_first) {
+  auto check_in = [&](const Tensor &t, const char *name) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+                    t.dim() == 2 && t.is_contiguous() && t.numel() > 0 &&
+                    t.size(1) % 8 == 0 && ((uintptr_t)t.data_ptr() & 15) == 0,
+                name, " must be a contiguous 16-byte aligned bf16 GPU matrix "
+                      "whose row length is a multiple of 8");
+    check_same_device(t, a1, name);
+  };
+  check_in(a1, "a1");
+  check_in(b1, "b1");
+  check_in(a2, "a2");
+  check_in(b2, "b2");
+  const int64_t K1 = a1.size(0), M1 = a1.size(1), M2 = a2.size(0),
+                K2 = a2.size(1);
+  TORCH_CHECK(b1.size(0) == K1 && n1 >= 1 && n1 <= b1.size(1), "b1 shape");
+  TORCH_CHECK(b2.size(0) == K2 && n2 >= 1 && n2 <= b2.size(1), "b2 shape");
+  TORCH_CHECK(c1.is_cuda() && c1.scalar_type() == at::kFloat &&
+                  c1.dim() == 3 && c1.is_contiguous() && c1.size(0) >= 1 &&
+                  c1.size(1) == M1 && c1.size(2) == n1,
+              "c1 must be contiguous fp32 [splits][M1][n1]");
+  check_same_device(c1, a1, "c1");
+  TORCH_CHECK(c2.is_cuda() && c2.is_contiguous(), "c2 must be contiguous");
+  check_same_device(c2, a1, "c2");
+  int64_t s2 = 1;
+  if (c2.scalar_type() == at::kFloat) {
+    TORCH_CHECK(c2.dim() == 3 && c2.size(0) >= 2 && c2.size(1) == M2 &&
+                    c2.size(2) == n2, "fp32 c2 must be [splits >= 2][M2][n2]");
+    s2 = c2.size(0);
+  } else {
+    TORCH_CHECK(c2.scalar_type() == at::kBFloat16 && c2.dim() == 2 &&
+                    c2.size(0) == M2 && c2.size(1) == n2,
+                "bf16 c2 must be [M2][n2]");
+  }
+  const HIPDeviceGuard guard(a1.device());
+  // the launcher refuses split counts above the k-tile count (the slabs
+  // would not all be written)
+  CHK(pipe8_gemm_pair(a1.data_ptr(), b1.data_ptr(), c1.data_ptr<float>(),
+                      (int)M1, (int)n1, (int)K1, b1.size(1), (int)c1.size(0),
+                      a2.data_ptr(), b2.data_ptr(), c2.data_ptr(), (int)M2,
+                      (int)n2, (int)K2, b2.size(1), (int)s2, paired ? 1 : 0,
+                      second_first ? 1 : 0, cur_stream()));
+}
+
 // bn_fwd_train consuming a pre-computed stats slab [rows][2][C] (skips
 // partials); the row count travels with the tensor
 static std::vector<Tensor> bn_fwd_train_pre(
@@ -2147,6 +2293,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stride"), py::arg("pad"), py::arg("fuse_splitk") = true,
         py::arg("fuse_epilogue") = true);
   m.def("conv2d_dgrad_bn", &conv2d_dgrad_bn);
+  m.def("conv2d_dgrad_wgrad", &conv2d_dgrad_wgrad);
+  m.def("conv2d_dgrad_bn_wgrad", &conv2d_dgrad_bn_wgrad);
+  // a stride-1 conv's dgrad and wgrad GEMMs as one grid (default) or as the
+  // two launches they were; dgrad_first orders the workgroups within the grid.
+  // Returns the mode it replaces, as MPIAMD_PAIR_BWD numbers them: 0 two
+  // launches, 1 one grid wgrad first, 2 one grid dgrad first; so
+  // set_pair_bwd(prev != 0, prev == 2) restores it.
+  m.def("set_pair_bwd", [](bool on, bool dgrad_first) {
+    return conv_set_pair_bwd(on ? (dgrad_first ? 2 : 1) : 0);
+  }, py::arg("on"), py::arg("dgrad_first") = false);
+  m.def("pipe8_gemm_pair", &pipe8_gemm_pair_b, py::arg("a1"), py::arg("b1"),
+        py::arg("c1"), py::arg("n1"), py::arg("a2"), py::arg("b2"),
+        py::arg("c2"), py::arg("n2"), py::arg("paired"),
+        py::arg("second_first") = false);
+  // (problem, tile, split) of workgroup b of a paired launch (launchers.h)
+  m.def("pair_decode", [](int b, int nblk1, int nwg1, int cpx1, int nblk2,
+                          int nwg2, int cpx2, bool second_first) {
+    const PairWg g = pair_decode(b, nblk1, nwg1, cpx1, nblk2, nwg2, cpx2,
+                                 second_first ? 1 : 0);
+    return py::make_tuple(g.problem, g.tile, g.split);
+  });
   m.def("bn_bwd_pre", &bn_bwd_pre);
   m.def("join_bwd_stats", &join_bwd_stats);
   m.def("bn_fwd_train_pre", &bn_fwd_train_pre);

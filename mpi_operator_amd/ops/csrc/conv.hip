@@ -729,3 +729,161 @@ extern "C" hipError_t conv_wgrad_implicit(const void *dy, const void *x,
   if (e != hipSuccess) return e;
   return splitk_reduce(partial, splits, (long)Kout * RSC, dw, dw_bf16, strm);
 }
+
+// ---- paired backward: a stride-1 conv's dgrad and wgrad GEMMs in one grid --
+// Process-wide switch, set through the extension's set_pair_bwd(); the
+// Python side owns MPIAMD_PAIR_BWD and calls this once at load.
+// 0: two launches; 1: one grid, wgrad workgroups first; 2: dgrad first.
+static std::atomic<int> g_pair_bwd{1};
+
+extern "C" int conv_set_pair_bwd(int mode) {
+  return g_pair_bwd.exchange(mode < 0 || mode > 2 ? 0 : mode,
+                             std::memory_order_relaxed);
+}
+
+// Whether this conv's dgrad and wgrad both run on the 8-wave pipeline, the
+// only kernel with a pair form: any knob that takes one of them elsewhere
+// keeps the two launches of conv_wgrad_implicit and conv_dgrad.
+static int conv_pair_mode(int R, int S, int pad) {
+  const bool plain = R == 1 && S == 1 && pad == 0;
+  const bool pipe8 = use_pipe8() && use_pipemix() &&
+                     (plain || (use_pipegather() && use_pipegather_wgrad()));
+  return pipe8 ? g_pair_bwd.load(std::memory_order_relaxed) : 0;
+}
+
+// The two GEMMs as one grid, both unreduced: dgrad into dx (bf16) or, when
+// *dsplits > 1, fp32 slabs in dpartial; wgrad always into fp32 slabs in
+// wpartial. Split counts are clamped as conv_dgrad_impl and
+// conv_wgrad_implicit clamp them.
+static hipError_t conv_dgrad_wgrad_pair(const void *dy, const void *w,
+                                        const void *x, void *dx, int N, int H,
+                                        int W, int C, int Kout, int R, int S,
+                                        int pad, int HO, int WO, int *dsplits,
+                                        float *dpartial, int *wsplits,
+                                        float *wpartial, bool dgrad_first,
+                                        hipStream_t strm) {
+  const long M = (long)N * H * W, Mo = (long)N * HO * WO;
+  const int Kd = R * S * Kout, RSC = R * S * C;
+  const int dsp = *dsplits = clamp_splits(*dsplits, Kd, BK);
+  const int wsp = *wsplits = clamp_splits(*wsplits, Mo, BK);
+  void *dout = dsp > 1 ? (void *)dpartial : dx;
+  const LinearWriter wwr{(long)RSC}, dwr{(long)C};
+  if (R == 1 && S == 1 && pad == 0) {
+    Pm8Gemm<Tn8Pipe<PlainTnSrc>, Tn8Pipe<PlainTnSrc>, LinearWriter> gw{
+        {{(const uint16_t *)dy, (long)Kout, (int)Mo, Kout}},
+        {{(const uint16_t *)x, (long)C, (int)Mo, RSC}},
+        wpartial, Kout, RSC, (int)Mo, wwr, RSC, wsp};
+    Pm8Gemm<Nt8Pipe<PlainNtSrc>, Tn8Pipe<PlainTnSrc>, LinearWriter> gd{
+        {{(const uint16_t *)dy, (long)Kout, (int)M, Kout}},
+        {{(const uint16_t *)w, (long)C, Kout, C}},
+        dout, (int)M, C, Kout, dwr, C, dsp};
+    return launch_pipe_mix8_pair_wr(gw, gd, dsp > 1, dgrad_first, strm);
+  }
+  Pm8Gemm<Tn8Pipe<PlainTnSrc>, Tn8Pipe<XcolSrc>, LinearWriter> gw{
+      {{(const uint16_t *)dy, (long)Kout, (int)Mo, Kout}},
+      {{(const uint16_t *)x, H, W, C, HO, WO, S, 1, pad, RSC, Mo}},
+      wpartial, Kout, RSC, (int)Mo, wwr, RSC, wsp};
+  Pm8Gemm<Nt8Pipe<ConvDgradSrc<1>>, Tn8Pipe<DgradWTnSrc>, LinearWriter> gd{
+      {{(const uint16_t *)dy, H, W, Kout, HO, WO, S, pad, Kd, M}},
+      {{(const uint16_t *)w, C, Kout, Kd, RSC}},
+      dout, (int)M, C, Kd, dwr, C, dsp};
+  return launch_pipe_mix8_pair_wr(gw, gd, dsp > 1, dgrad_first, strm);
+}
+
+// Test hook: the two GEMM kinds of a 1x1 pair on plain matrices, unreduced,
+// as one grid (paired) or as the two launch_pipe_mix8_wr launches. The conv
+// entry points above always give both problems of a grid the same epilogue
+// (channel counts are multiples of 8 and every output is freshly allocated);
+// here N and the output pointers are the caller's, so each of the launcher's
+// epilogue mixes can be driven and compared with the separate launches.
+//   problem 1: c1 [splits1][M1][N1] fp32 = a1^T · b1, a1 [K1][M1], b1 [K1][ldb1]
+//   problem 2: c2 [M2][N2] bf16 (splits2 <= 1) or [splits2][M2][N2] fp32
+//              = a2 · b2, a2 [M2][K2], b2 [K2][ldb2]
+// splits must already be clamped (clamp_splits) so the caller sized c for them.
+extern "C" hipError_t pipe8_gemm_pair(const void *a1, const void *b1, float *c1,
+                                      int M1, int N1, int K1, long ldb1,
+                                      int splits1, const void *a2,
+                                      const void *b2, void *c2, int M2, int N2,
+                                      int K2, long ldb2, int splits2,
+                                      int paired, int second_first,
+                                      hipStream_t strm) {
+  if (splits1 != clamp_splits(splits1, K1, BK) ||
+      splits2 != clamp_splits(splits2, K2, BK))
+    return hipErrorInvalidValue;
+  const LinearWriter wr1{(long)N1}, wr2{(long)N2};
+  Pm8Gemm<Tn8Pipe<PlainTnSrc>, Tn8Pipe<PlainTnSrc>, LinearWriter> g1{
+      {{(const uint16_t *)a1, (long)M1, K1, M1}},
+      {{(const uint16_t *)b1, ldb1, K1, N1}},
+      c1, M1, N1, K1, wr1, N1, splits1};
+  Pm8Gemm<Nt8Pipe<PlainNtSrc>, Tn8Pipe<PlainTnSrc>, LinearWriter> g2{
+      {{(const uint16_t *)a2, (long)K2, M2, K2}},
+      {{(const uint16_t *)b2, ldb2, K2, N2}},
+      c2, M2, N2, K2, wr2, N2, splits2};
+  if (paired)
+    return launch_pipe_mix8_pair_wr(g1, g2, splits2 > 1, second_first != 0,
+                                    strm);
+  hipError_t e = launch_pipe_mix8_wr(g1.sa, g1.sb, g1.c, M1, N1, K1, wr1, N1,
+                                     true, strm, splits1);
+  if (e != hipSuccess) return e;
+  return launch_pipe_mix8_wr(g2.sa, g2.sb, g2.c, M2, N2, K2, wr2, N2,
+                             splits2 > 1, strm, splits2);
+}
+
+// conv_wgrad_implicit (bf16 dw) + conv_dgrad of a stride-1 conv
+extern "C" hipError_t conv_dgrad_wgrad(const void *dy, const void *w,
+                                       const void *x, void *dx, void *dw,
+                                       int N, int H, int W, int C, int Kout,
+                                       int R, int S, int pad, int HO, int WO,
+                                       int dsplits, float *dpartial,
+                                       int wsplits, float *wpartial,
+                                       hipStream_t strm) {
+  const int mode = conv_pair_mode(R, S, pad);
+  hipError_t e;
+  if (!mode) {
+    e = conv_wgrad_implicit(dy, x, wpartial, dw, N, H, W, C, Kout, R, S, 1,
+                            pad, HO, WO, wsplits, 1, strm);
+    if (e != hipSuccess) return e;
+    return conv_dgrad(dy, w, dx, N, H, W, C, Kout, R, S, 1, pad, HO, WO,
+                      dsplits, dpartial, strm);
+  }
+  e = conv_dgrad_wgrad_pair(dy, w, x, dx, N, H, W, C, Kout, R, S, pad, HO, WO,
+                            &dsplits, dpartial, &wsplits, wpartial, mode == 2,
+                            strm);
+  if (e != hipSuccess) return e;
+  if (dsplits > 1) {
+    e = splitk_reduce(dpartial, dsplits, (long)N * H * W * C, dx, 1, strm);
+    if (e != hipSuccess) return e;
+  }
+  return splitk_reduce(wpartial, wsplits, (long)Kout * R * S * C, dw, 1, strm);
+}
+
+// conv_wgrad_implicit (bf16 dw) + conv_dgrad_bn of a stride-1 conv; the
+// dgrad must split (conv_dgrad_bn_rows() != 0), as for conv_dgrad_bn
+extern "C" hipError_t conv_dgrad_bn_wgrad(
+    const void *dy, const void *w, const void *x, void *dx, void *dw, int N,
+    int H, int W, int C, int Kout, int R, int S, int pad, int HO, int WO,
+    int dsplits, float *dpartial, int wsplits, float *wpartial, const void *bx,
+    const void *by, const uint8_t *mask, const float *mean,
+    const float *invstd, int relu, float *bn_slab, hipStream_t strm) {
+  const int mode = conv_pair_mode(R, S, pad);
+  hipError_t e;
+  if (!mode) {
+    e = conv_wgrad_implicit(dy, x, wpartial, dw, N, H, W, C, Kout, R, S, 1,
+                            pad, HO, WO, wsplits, 1, strm);
+    if (e != hipSuccess) return e;
+    return conv_dgrad_bn(dy, w, dx, N, H, W, C, Kout, R, S, pad, HO, WO,
+                         dsplits, dpartial, bx, by, mask, mean, invstd, relu,
+                         bn_slab, strm);
+  }
+  if (clamp_splits(dsplits, R * S * Kout, BK) <= 1)
+    return hipErrorInvalidValue; // conv_dgrad_bn_rows() == 0
+  e = conv_dgrad_wgrad_pair(dy, w, x, dx, N, H, W, C, Kout, R, S, pad, HO, WO,
+                            &dsplits, dpartial, &wsplits, wpartial, mode == 2,
+                            strm);
+  if (e != hipSuccess) return e;
+  e = bn_reduce_stats_bwd_launch(dpartial, dsplits, dx, bx, by, mask, mean,
+                                 invstd, relu, bn_slab, (long)N * H * W, C,
+                                 strm);
+  if (e != hipSuccess) return e;
+  return splitk_reduce(wpartial, wsplits, (long)Kout * R * S * C, dw, 1, strm);
+}

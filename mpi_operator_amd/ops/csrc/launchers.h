@@ -41,6 +41,27 @@ static inline long embed_bwd_chunks(long n) {
 // edges its tests probe.
 constexpr int MLM_SELECT_TILE = 2048;
 
+// Workgroup b of a paired GEMM launch (pipe_mix.h pipe_mix8_pair_k): a 1-D
+// grid whose first nblk1 = nwg1 * splits1 workgroups are problem 1 and the
+// rest problem 2 (dgrad_first: the first nwg2 * splits2 are problem 2). Within
+// a problem the local index decodes as blockIdx of the problem's own
+// dim3(nwg, splits) grid does, x fastest, with the same XCD fold (cpx = 0:
+// none). Host and device; the extension's pair_decode exposes it to the tests.
+struct PairWg {
+  int problem, tile, split; // problem 0 or 1
+};
+__host__ __device__ inline PairWg pair_decode(int b, int nblk1, int nwg1,
+                                              int cpx1, int nblk2, int nwg2,
+                                              int cpx2, int second_first) {
+  if (second_first) b = b < nblk2 ? b + nblk1 : b - nblk2;
+  const int problem = b >= nblk1;
+  const int local = problem ? b - nblk1 : b;
+  const int nwg = problem ? nwg2 : nwg1, cpx = problem ? cpx2 : cpx1;
+  int tile = local % nwg;
+  if (cpx) tile = (tile & 7) * cpx + (tile >> 3);
+  return {problem, tile, local / nwg};
+}
+
 extern "C" {
 
 // ---- elementwise.hip ----
@@ -294,6 +315,33 @@ hipError_t conv_wgrad_implicit(const void *dy, const void *x, float *partial,
                                int R, int S, int stride, int pad, int HO,
                                int WO, int splits, int dw_bf16,
                                hipStream_t strm);
+// stride-1 conv backward, both gradients: what conv_wgrad_implicit (bf16 dw)
+// followed by conv_dgrad / conv_dgrad_bn computes, bit for bit, with the two
+// GEMMs launched as one grid under conv_set_pair_bwd. mode 0: two launches,
+// 1: one grid with the wgrad workgroups first, 2: dgrad first; returns the
+// previous mode.
+int conv_set_pair_bwd(int mode);
+hipError_t conv_dgrad_wgrad(const void *dy, const void *w, const void *x,
+                            void *dx, void *dw, int N, int H, int W, int C,
+                            int Kout, int R, int S, int pad, int HO, int WO,
+                            int dsplits, float *dpartial, int wsplits,
+                            float *wpartial, hipStream_t strm);
+hipError_t conv_dgrad_bn_wgrad(const void *dy, const void *w, const void *x,
+                               void *dx, void *dw, int N, int H, int W, int C,
+                               int Kout, int R, int S, int pad, int HO, int WO,
+                               int dsplits, float *dpartial, int wsplits,
+                               float *wpartial, const void *bx, const void *by,
+                               const uint8_t *mask, const float *mean,
+                               const float *invstd, int relu, float *bn_slab,
+                               hipStream_t strm);
+// test hook: the two GEMM kinds of a 1x1 pair on plain matrices, unreduced;
+// one grid (paired) or the two separate 8-wave launches. N and the output
+// pointers are the caller's, so the two problems can take different epilogues.
+hipError_t pipe8_gemm_pair(const void *a1, const void *b1, float *c1, int M1,
+                           int N1, int K1, long ldb1, int splits1,
+                           const void *a2, const void *b2, void *c2, int M2,
+                           int N2, int K2, long ldb2, int splits2, int paired,
+                           int second_first, hipStream_t strm);
 
 // ---- layernorm.hip ----
 hipError_t ln_fwd(const void *x, const float *gamma, const float *beta,

@@ -697,21 +697,24 @@ template <class SRC> struct Tn8Pipe {
 // through its own 8 KiB slice of the (now dead) operand images and issues
 // 16-byte stores; chosen per launch by launch_pipe_mix8_wr. VEC = false is
 // the one-element-per-lane epilogue, unchanged.
-template <class SA, class SB, bool C_F32, class WR, bool VEC = false>
-__global__ __launch_bounds__(512) void pipe_mix8_k(
-    SA sa, SB sb, void *__restrict__ cptr, int M, int N, int K, WR wrt,
-    int tiles_n, int kt_per_split, long split_stride, int xcd_cpx, int swap,
-    const uint16_t *__restrict__ zeros) {
-  int tile = swap ? blockIdx.y : blockIdx.x;
-  int split = swap ? blockIdx.x : blockIdx.y;
-  if (xcd_cpx) tile = (tile & 7) * xcd_cpx + (tile >> 3);
+//
+// The work of ONE workgroup is pipe_mix8_body: output tile `tile` (already
+// XCD-folded), split-K slice `split`, the 64 KiB operand images at `lds`
+// (128-B aligned: the tr_b16 read resolves its block as addr & ~127).
+// pipe_mix8_k runs it on a (tiles, splits) grid; pipe_mix8_pair_k below
+// runs two independent GEMMs' workgroups in one grid.
+template <class SA, class SB, bool C_F32, class WR, bool VEC>
+DEV_INLINE void pipe_mix8_body(SA sa, SB sb, void *__restrict__ cptr, int M,
+                               int N, int K, WR wrt, int tiles_n,
+                               int kt_per_split, long split_stride,
+                               const uint16_t *__restrict__ zeros, int tile,
+                               int split, ushort8 *lds) {
   int tm = tile / tiles_n, tn = tile % tiles_n;
   int row0 = tm * PM_BM, col0 = tn * PM_BM;
   int tid = threadIdx.x;
   int lane = tid & 63, wave = tid >> 6;
   int wr = wave >> 2, wc = wave & 3; // 2×4: wave C = 64M × 32N
 
-  __shared__ __align__(128) ushort8 lds[8 * PM_HSZ];
   if constexpr (WR::STATS) wrt.reset();
 #define PM8_IMG(buf, op, kh) (lds + (((buf) * 2 + (op)) * 2 + (kh)) * PM_HSZ)
 
@@ -819,6 +822,20 @@ __global__ __launch_bounds__(512) void pipe_mix8_k(
 }
 #undef PM8_IMG
 
+template <class SA, class SB, bool C_F32, class WR, bool VEC = false>
+__global__ __launch_bounds__(512) void pipe_mix8_k(
+    SA sa, SB sb, void *__restrict__ cptr, int M, int N, int K, WR wrt,
+    int tiles_n, int kt_per_split, long split_stride, int xcd_cpx, int swap,
+    const uint16_t *__restrict__ zeros) {
+  int tile = swap ? blockIdx.y : blockIdx.x;
+  int split = swap ? blockIdx.x : blockIdx.y;
+  if (xcd_cpx) tile = (tile & 7) * xcd_cpx + (tile >> 3);
+  __shared__ __align__(128) ushort8 lds[8 * PM_HSZ];
+  pipe_mix8_body<SA, SB, C_F32, WR, VEC>(sa, sb, cptr, M, N, K, wrt, tiles_n,
+                                         kt_per_split, split_stride, zeros,
+                                         tile, split, lds);
+}
+
 template <class SA8, class SB8, class WR>
 static hipError_t launch_pipe_mix8_wr(const SA8 &sa, const SB8 &sb, void *c,
                                       int M, int N, int K, const WR &wrt,
@@ -841,5 +858,112 @@ static hipError_t launch_pipe_mix8_wr(const SA8 &sa, const SB8 &sb, void *c,
     if (vec) with_bool(c_f32, [&](auto f32) { launch(f32, std::true_type{}); });
   }
   if (!vec) with_bool(c_f32, [&](auto f32) { launch(f32, std::false_type{}); });
+  return hipGetLastError();
+}
+
+// ======================================================================
+// Two independent 8-wave GEMMs in ONE grid (conv backward: the dgrad and
+// the wgrad of a conv both read dy and neither reads the other's output).
+// Each workgroup is exactly one workgroup of one of the two separate
+// launches — same tile, split, K range and epilogue, so every output bit
+// is the separate launches' — but workgroups of the second problem start
+// as those of the first retire: one problem's epilogue stores overlap the
+// other's operand loads, and the drain/ramp between two launches is gone.
+// No atomics, no flags, no workgroup waits on another. The problem is
+// chosen block-uniformly from blockIdx.x before any barrier (launchers.h
+// pair_decode); both bodies share the one 64 KiB LDS array.
+// ======================================================================
+
+// One GEMM of a pair as launch_pipe_mix8_wr takes it.
+template <class SA8, class SB8, class WR> struct Pm8Gemm {
+  SA8 sa;
+  SB8 sb;
+  void *c;
+  int M, N, K;
+  WR wrt;
+  long ldc;
+  int splits;
+};
+
+// Device-side argument block of one problem; C_F32 / VEC as pipe_mix8_k.
+template <class SA, class SB, bool C_F32, class WR, bool VEC> struct Pm8Body {
+  SA sa;
+  SB sb;
+  void *cptr;
+  int M, N, K;
+  WR wrt;
+  int tiles_n, kt_per_split;
+  long split_stride;
+  DEV_INLINE void run(const uint16_t *zeros, int tile, int split,
+                      ushort8 *lds) const {
+    pipe_mix8_body<SA, SB, C_F32, WR, VEC>(sa, sb, cptr, M, N, K, wrt,
+                                           tiles_n, kt_per_split,
+                                           split_stride, zeros, tile, split,
+                                           lds);
+  }
+};
+
+template <class Body1, class Body2>
+__global__ __launch_bounds__(512) void pipe_mix8_pair_k(
+    Body1 p1, Body2 p2, int nblk1, int nwg1, int cpx1, int nblk2, int nwg2,
+    int cpx2, int second_first, const uint16_t *__restrict__ zeros) {
+  __shared__ __align__(128) ushort8 lds[8 * PM_HSZ];
+  const PairWg wg = pair_decode(blockIdx.x, nblk1, nwg1, cpx1, nblk2, nwg2,
+                                cpx2, second_first);
+  if (wg.problem == 0)
+    p1.run(zeros, wg.tile, wg.split, lds);
+  else
+    p2.run(zeros, wg.tile, wg.split, lds);
+}
+
+// g1 writes fp32 (a split-K slab set: the wgrad side), g2 fp32 iff c2_f32.
+// second_first puts g2's workgroups at the front of the grid. The caller
+// has already established that both problems take the 8-wave route.
+// Each problem's epilogue is decided on its own, as launch_pipe_mix8_wr
+// decides it, so the pair is instantiated for every (VEC1, C_F32 of g2, VEC2).
+// The conv callers give both problems the same VEC on every launch (channel
+// counts are multiples of 8, outputs fresh allocations); the mixed grids are
+// reached, and tested, through the pipe8_gemm_pair hook only.
+template <class SA1, class SB1, class WR1, class SA2, class SB2, class WR2>
+static hipError_t launch_pipe_mix8_pair_wr(const Pm8Gemm<SA1, SB1, WR1> &g1,
+                                           const Pm8Gemm<SA2, SB2, WR2> &g2,
+                                           bool c2_f32, bool second_first,
+                                           hipStream_t s) {
+  const uint16_t *zeros = pm_zeros_page();
+  if (!zeros) return hipErrorOutOfMemory;
+  const TileGeom t1(g1.M, g1.N, g1.K, g1.ldc, g1.splits, PM_BM, PM_BK);
+  const TileGeom t2(g2.M, g2.N, g2.K, g2.ldc, g2.splits, PM_BM, PM_BK);
+  const int nblk1 = t1.nwg * t1.splits, nblk2 = t2.nwg * t2.splits;
+  bool vec1 = false, vec2 = false;
+  if constexpr (WR1::VEC)
+    vec1 = epilogue_vec_eligible(g1.wrt, g1.c, g1.N, true, t1.splits,
+                                 t1.split_stride);
+  if constexpr (WR2::VEC)
+    vec2 = epilogue_vec_eligible(g2.wrt, g2.c, g2.N, c2_f32, t2.splits,
+                                 t2.split_stride);
+  auto launch = [&](auto v1, auto f2, auto v2) {
+    using B1 = Pm8Body<SA1, SB1, true, WR1, decltype(v1)::value>;
+    using B2 = Pm8Body<SA2, SB2, decltype(f2)::value, WR2, decltype(v2)::value>;
+    B1 b1{g1.sa, g1.sb, g1.c, g1.M, g1.N, g1.K, g1.wrt,
+          t1.tiles_n, t1.kts, t1.split_stride};
+    B2 b2{g2.sa, g2.sb, g2.c, g2.M, g2.N, g2.K, g2.wrt,
+          t2.tiles_n, t2.kts, t2.split_stride};
+    pipe_mix8_pair_k<B1, B2><<<nblk1 + nblk2, 512, 0, s>>>(
+        b1, b2, nblk1, t1.nwg, t1.cpx(use_sk_cpx()), nblk2, t2.nwg,
+        t2.cpx(use_sk_cpx()), second_first ? 1 : 0, zeros);
+  };
+  // the VEC bodies exist only for writers that have a row-major epilogue
+  auto with_vec = [](bool v, auto has, auto &&f) {
+    if constexpr (decltype(has)::value) {
+      if (v) return f(std::true_type{});
+    }
+    f(std::false_type{});
+  };
+  with_vec(vec1, std::bool_constant<WR1::VEC>{}, [&](auto v1) {
+    with_bool(c2_f32, [&](auto f2) {
+      with_vec(vec2, std::bool_constant<WR2::VEC>{},
+               [&](auto v2) { launch(v1, f2, v2); });
+    });
+  });
   return hipGetLastError();
 }

@@ -178,18 +178,26 @@ class BottleneckFn(torch.autograd.Function):
         # (bn_bwd's relu path reads `out` anyway) — the old materialized
         # g = dout·(out>0) was pure data movement (2 extra passes/block).
 
-        def dgrad_bn(dyo, w, st_, pad, a, y, g, m, v, mk):
-            """dgrad feeding a BN(+ReLU) backward: a split-K dgrad's reduce
-            also emits that BN's partial-stats slab; an empty slab (unsplit
-            or stride-2 dgrad) takes the partials pass."""
-            if not _FUSEBN_BWD or st_ != 1:
-                dy = ext.conv2d_dgrad(dyo, w, y.shape[2], y.shape[3], st_, pad)
-                return ext.bn_bwd(dy, a, y, g, m, v, True, mk)
-            dy, slab = ext.conv2d_dgrad_bn(dyo, w, y.shape[2], y.shape[3],
-                                           st_, pad, a, y, m, v, True, mk)
+        def conv_bwd_bn(dyo, w, R, st_, pad, a, y, g, m, v, mk):
+            """Backward of a conv whose input y is the output of a BN(+ReLU)
+            layer: (dw, dx, dgamma, dbeta), dx through that BN. Stride 1
+            takes both conv gradients from one call (their GEMMs share a
+            launch, MPIAMD_PAIR_BWD), and a split-K dgrad's reduce also emits
+            the BN's partial-stats slab; an empty slab (unsplit dgrad) takes
+            the partials pass, as does stride 2."""
+            H, W = y.shape[2], y.shape[3]
+            if st_ != 1:
+                dw = ext.conv2d_wgrad(y, dyo, R, R, st_, pad)
+                dy = ext.conv2d_dgrad(dyo, w, H, W, st_, pad)
+                return (dw, *ext.bn_bwd(dy, a, y, g, m, v, True, mk))
+            if not _FUSEBN_BWD:
+                dy, dw = ext.conv2d_dgrad_wgrad(dyo, w, y, H, W, R, R, pad)
+                return (dw, *ext.bn_bwd(dy, a, y, g, m, v, True, mk))
+            dy, slab, dw = ext.conv2d_dgrad_bn_wgrad(dyo, w, y, H, W, R, R,
+                                                     pad, a, y, m, v, True, mk)
             if slab.numel() > 0:
-                return ext.bn_bwd_pre(dy, slab, a, y, g, m, v, True, mk)
-            return ext.bn_bwd(dy, a, y, g, m, v, True, mk)
+                return (dw, *ext.bn_bwd_pre(dy, slab, a, y, g, m, v, True, mk))
+            return (dw, *ext.bn_bwd(dy, a, y, g, m, v, True, mk))
 
         def bn_bwd_join(slab, a, g, m, v):
             """BN backward of a layer whose dy is dout: from the slab the
@@ -202,20 +210,22 @@ class BottleneckFn(torch.autograd.Function):
         if ctx.link_out is not None:
             slab3, slabd = ctx.link_out.take(dout)
         dx3, dg3, db3 = bn_bwd_join(slab3, a3, g3, m3, v3)
-        dw3 = ext.conv2d_wgrad(y2, dx3, 1, 1, 1, 0)
-        dx2, dg2, db2 = dgrad_bn(dx3, w3, 1, 0, a2, y2, g2, m2, v2, mk2)
-        dw2 = ext.conv2d_wgrad(y1, dx2, 3, 3, st, 1)
-        dx1, dg1, db1 = dgrad_bn(dx2, w2, st, 1, a1, y1, g1, m1, v1, mk1)
-        dw1 = ext.conv2d_wgrad(x, dx1, 1, 1, 1, 0)
-
-        dx0 = ext.conv2d_dgrad(dx1, w1, x.shape[2], x.shape[3], 1, 0)
+        dw3, dx2, dg2, db2 = conv_bwd_bn(dx3, w3, 1, 1, 0, a2, y2, g2, m2,
+                                         v2, mk2)
+        dw2, dx1, dg1, db1 = conv_bwd_bn(dx2, w2, 3, st, 1, a1, y1, g1, m1,
+                                         v1, mk1)
+        H, W = x.shape[2], x.shape[3]
+        dx0, dw1 = ext.conv2d_dgrad_wgrad(dx1, w1, x, H, W, 1, 1, 0)
         if ctx.has_ds:
             # mask from the join output (the downsample BN itself has no
             # ReLU): dy_ds = dout·(out>0), applied inside bn_bwd
             # the join mask (out>0) is bn3's mask
             dad, dgd, dbd = bn_bwd_join(slabd, ad, gd, md, vd)
-            dwd = ext.conv2d_wgrad(x, dad, 1, 1, st, 0)
-            skip = ext.conv2d_dgrad(dad, wd, x.shape[2], x.shape[3], st, 0)
+            if st == 1:
+                skip, dwd = ext.conv2d_dgrad_wgrad(dad, wd, x, H, W, 1, 1, 0)
+            else:
+                dwd = ext.conv2d_wgrad(x, dad, 1, 1, st, 0)
+                skip = ext.conv2d_dgrad(dad, wd, H, W, st, 0)
             ja, jmask = skip, _empty()  # dxt = skip + dx0
         else:
             dwd = dgd = dbd = None
