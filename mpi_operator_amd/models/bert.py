@@ -93,6 +93,14 @@ class BertConfig:
     # published recipe), applied in train(): drawn inside the attention
     # kernels on GPU bf16, F.dropout on the eager chain's probs otherwise.
     attn_dropout: float = 0.0
+    # Causal (autoregressive) self-attention: token i attends to the tokens
+    # j <= i of its own sequence. GPU bf16 with head_dim 64 runs the causal
+    # flash kernels (Fx.flash_attention / _varlen, causal=True) at any
+    # sequence length, packed or with no mask or the [b, 1, 1, s] key mask,
+    # provided attention dropout has its rng (p == 0 or rng given); any
+    # other mask shape, dtype or device takes the eager chains, which
+    # exclude the upper triangle themselves.
+    causal: bool = False
     eps: float = 1e-12
 
 
@@ -132,6 +140,7 @@ class SelfAttention(nn.Module):
         super().__init__()
         self.heads = cfg.heads
         self.head_dim = cfg.hidden // cfg.heads
+        self.causal = cfg.causal
         # fused QKV: one big GEMM instead of three (3× fewer kernel launches,
         # one pass over the activations)
         self.qkv = BertLinear(cfg.hidden, 3 * cfg.hidden)
@@ -147,7 +156,7 @@ class SelfAttention(nn.Module):
             # no host read of cu_seqlens: graph-safe
             ctx = Fx.flash_attention_varlen(
                 qkv.view(t, 3, nh, hd), cu_seqlens, max_seqlen, nh, self.scale,
-                p, rng, site)
+                p, rng, site, self.causal)
             return ctx.view(1, t, nh * hd)
         # eager per-sequence chain (reads cu_seqlens on the host)
         cu = [int(c) for c in cu_seqlens.tolist()]
@@ -157,6 +166,9 @@ class SelfAttention(nn.Module):
                 continue
             q, k, v = (qkv[0, a:e, i].transpose(0, 1) for i in range(3))
             scores = torch.matmul(q, k.transpose(-1, -2)) * self.scale
+            if self.causal:
+                scores = scores.masked_fill(self._future(e - a, q.device),
+                                            float("-inf"))
             probs = torch.softmax(scores.float(), dim=-1).to(v.dtype)
             if p > 0:
                 probs = F.dropout(probs, p, training=True)
@@ -165,6 +177,11 @@ class SelfAttention(nn.Module):
         if cu[-1] < t:
             parts.append(qkv.new_zeros(t - cu[-1], nh * hd))
         return torch.cat(parts, dim=0)[None]
+
+    @staticmethod
+    def _future(s, device):
+        """bool [s, s], True where key j lies in the future of row i."""
+        return torch.ones(s, s, dtype=torch.bool, device=device).triu(1)
 
     def forward(self, x, attn_mask=None, p=0.0, rng=None, site=0, *,
                 cu_seqlens=None, max_seqlen=None):
@@ -189,13 +206,22 @@ class SelfAttention(nn.Module):
             return self.out(self._packed(
                 qkv, cu_seqlens, s if max_seqlen is None else max_seqlen, hip,
                 p, rng, site))
-        if hip and s <= 256 and attn_mask is None:
+        if self.causal and hip and (attn_mask is None
+                                    or attn_mask.shape == (b, 1, 1, s)):
+            # the causal kernels exist in flash_attention.hip only: any s,
+            # whatever MPIAMD_FLASH_ATTN says
+            return self.out(Fx.flash_attention(
+                qkv, self.heads, self.scale,
+                attn_mask.reshape(b, s) if attn_mask is not None else None,
+                p, rng, site, True))
+        if hip and s <= 256 and attn_mask is None and not self.causal:
             # fused QKᵀ→softmax→PV kernel (one launch per step instead of
             # the batched-matmul + softmax chain); emits ctx in [b, s, h]
             # directly — no transpose/reshape passes
             return self.out(Fx.attention(qkv, self.heads, self.scale, None,
                                          p, rng, site))
-        if (hip and (attn_mask is None or attn_mask.shape == (b, 1, 1, s))
+        if (hip and not self.causal
+                and (attn_mask is None or attn_mask.shape == (b, 1, 1, s))
                 and _os.environ.get("MPIAMD_FLASH_ATTN",
                                     _FLASH_ATTN_DEFAULT) != "0"):
             # tiled online-softmax kernels: s > 256 and/or the additive key
@@ -209,6 +235,9 @@ class SelfAttention(nn.Module):
         scores = torch.matmul(q, k.transpose(-1, -2)) * self.scale
         if attn_mask is not None:
             scores = scores + attn_mask
+        if self.causal:
+            scores = scores.masked_fill(self._future(s, x.device),
+                                        float("-inf"))
         probs = torch.softmax(scores.float(), dim=-1).to(v.dtype)
         if p > 0:
             probs = F.dropout(probs, p, training=True)
@@ -250,7 +279,7 @@ class BertLayer(nn.Module):
         cu_seqlens, max_seqlen: x is a packed batch (SelfAttention.forward);
         everything but attention is token-major and takes it as it is."""
         if (x.is_cuda and x.dtype == torch.bfloat16 and attn_mask is None
-                and cu_seqlens is None
+                and cu_seqlens is None and not self.attn.causal
                 and self.attn.head_dim == 64 and x.shape[1] == 128 and p == 0
                 and attn_p == 0
                 and _os.environ.get("MPIAMD_LAYER_FUSED", "0") == "1"):

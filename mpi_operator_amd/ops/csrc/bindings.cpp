@@ -1485,7 +1485,8 @@ static Tensor flash_mask(const c10::optional<Tensor> &mask, long B, long S) {
 
 static std::vector<Tensor> flash_attn_fwd(const Tensor &qkv, int64_t heads,
                                           double scale,
-                                          const c10::optional<Tensor> &mask) {
+                                          const c10::optional<Tensor> &mask,
+                                          bool causal) {
   flash_check_qkv(qkv, heads);
   const HIPDeviceGuard guard(qkv.device());
   int B = qkv.size(0), S = qkv.size(1), H = qkv.size(3);
@@ -1495,14 +1496,14 @@ static std::vector<Tensor> flash_attn_fwd(const Tensor &qkv, int64_t heads,
   CHK(flash_attn_fwd_launch(
       qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr<float>(),
       maskc.defined() ? maskc.data_ptr<float>() : nullptr, B, S, H,
-      (float)scale, cur_stream()));
+      (float)scale, causal, cur_stream()));
   return {ctx, lse};
 }
 
 static Tensor flash_attn_bwd(const Tensor &qkv, const Tensor &ctx,
                              const Tensor &dctx, const Tensor &lse,
                              double scale,
-                             const c10::optional<Tensor> &mask) {
+                             const c10::optional<Tensor> &mask, bool causal) {
   flash_check_qkv(qkv, qkv.dim() == 5 ? qkv.size(3) : 0);
   const HIPDeviceGuard guard(qkv.device());
   int B = qkv.size(0), S = qkv.size(1), H = qkv.size(3);
@@ -1522,7 +1523,7 @@ static Tensor flash_attn_bwd(const Tensor &qkv, const Tensor &ctx,
       qkv.data_ptr(), ctx.data_ptr(), dc.data_ptr(), lse.data_ptr<float>(),
       delta.data_ptr<float>(),
       maskc.defined() ? maskc.data_ptr<float>() : nullptr, dqkv.data_ptr(), B,
-      S, H, (float)scale, cur_stream()));
+      S, H, (float)scale, causal, cur_stream()));
   return dqkv;
 }
 
@@ -1617,7 +1618,7 @@ static Tensor attn_drop_bwd_b(const Tensor &qkv, const Tensor &dctx,
 static std::vector<Tensor> flash_attn_drop_fwd_b(
     const Tensor &qkv, int64_t heads, double scale,
     const c10::optional<Tensor> &mask, const Tensor &state, double p,
-    int64_t site) {
+    int64_t site, bool causal) {
   const AttnDropShape d = check_attn_drop_qkv(qkv, heads, "qkv");
   check_rng_state(state, qkv);
   const DropParams dp = check_drop_params(p, site);
@@ -1630,7 +1631,7 @@ static std::vector<Tensor> flash_attn_drop_fwd_b(
                                  lse.data_ptr<float>(), mp,
                                  state.data_ptr<int64_t>(), dp.site, dp.thr,
                                  dp.scale, d.B, d.S, d.H, (float)scale,
-                                 cur_stream()));
+                                 causal, cur_stream()));
   return {ctx, lse};
 }
 
@@ -1640,7 +1641,7 @@ static Tensor flash_attn_drop_bwd_b(const Tensor &qkv, const Tensor &ctx,
                                     double scale,
                                     const c10::optional<Tensor> &mask,
                                     const Tensor &state, double p,
-                                    int64_t site) {
+                                    int64_t site, bool causal) {
   const AttnDropShape d = check_attn_drop_qkv(qkv, -1, "qkv");
   check_attn_ctx(ctx, qkv, d, "ctx");
   check_attn_ctx(dctx, qkv, d, "dctx");
@@ -1658,7 +1659,8 @@ static Tensor flash_attn_drop_bwd_b(const Tensor &qkv, const Tensor &ctx,
   CHK(flash_attn_drop_bwd_launch(
       qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr<float>(),
       delta.data_ptr<float>(), mp, state.data_ptr<int64_t>(), dp.site, dp.thr,
-      dp.scale, dqkv.data_ptr(), d.B, d.S, d.H, (float)scale, cur_stream()));
+      dp.scale, dqkv.data_ptr(), d.B, d.S, d.H, (float)scale, causal,
+      cur_stream()));
   return dqkv;
 }
 
@@ -1719,7 +1721,8 @@ static void check_varlen_drop_shape(const VarlenShape &d) {
 static std::vector<Tensor> flash_attn_varlen_fwd(const Tensor &qkv,
                                                  const Tensor &cu_seqlens,
                                                  int64_t max_seqlen,
-                                                 int64_t heads, double scale) {
+                                                 int64_t heads, double scale,
+                                                 bool causal) {
   const VarlenShape d = check_varlen_qkv(qkv, heads, cu_seqlens, max_seqlen);
   const HIPDeviceGuard guard(qkv.device());
   Tensor ctx = at::empty({d.T, (long)d.H * 64}, qkv.options());
@@ -1727,14 +1730,15 @@ static std::vector<Tensor> flash_attn_varlen_fwd(const Tensor &qkv,
   CHK(flash_attn_varlen_fwd_launch(
       qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr<float>(),
       cu_seqlens.data_ptr<int>(), d.N, d.T, d.max_seqlen, d.H, (float)scale,
-      cur_stream()));
+      causal, cur_stream()));
   return {ctx, lse};
 }
 
 static Tensor flash_attn_varlen_bwd(const Tensor &qkv, const Tensor &ctx,
                                     const Tensor &dctx, const Tensor &lse,
                                     const Tensor &cu_seqlens,
-                                    int64_t max_seqlen, double scale) {
+                                    int64_t max_seqlen, double scale,
+                                    bool causal) {
   const VarlenShape d = check_varlen_qkv(qkv, -1, cu_seqlens, max_seqlen);
   check_varlen_ctx(ctx, qkv, d, "ctx");
   check_varlen_ctx(dctx, qkv, d, "dctx");
@@ -1745,14 +1749,14 @@ static Tensor flash_attn_varlen_bwd(const Tensor &qkv, const Tensor &ctx,
   CHK(flash_attn_varlen_bwd_launch(
       qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr<float>(),
       delta.data_ptr<float>(), cu_seqlens.data_ptr<int>(), dqkv.data_ptr(),
-      d.N, d.T, d.max_seqlen, d.H, (float)scale, cur_stream()));
+      d.N, d.T, d.max_seqlen, d.H, (float)scale, causal, cur_stream()));
   return dqkv;
 }
 
 static std::vector<Tensor> flash_attn_varlen_drop_fwd_b(
     const Tensor &qkv, const Tensor &cu_seqlens, int64_t max_seqlen,
     int64_t heads, double scale, const Tensor &state, double p,
-    int64_t site) {
+    int64_t site, bool causal) {
   const VarlenShape d = check_varlen_qkv(qkv, heads, cu_seqlens, max_seqlen);
   check_varlen_drop_shape(d);
   check_rng_state(state, qkv);
@@ -1763,7 +1767,8 @@ static std::vector<Tensor> flash_attn_varlen_drop_fwd_b(
   CHK(flash_attn_varlen_drop_fwd_launch(
       qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr<float>(),
       cu_seqlens.data_ptr<int>(), state.data_ptr<int64_t>(), dp.site, dp.thr,
-      dp.scale, d.N, d.T, d.max_seqlen, d.H, (float)scale, cur_stream()));
+      dp.scale, d.N, d.T, d.max_seqlen, d.H, (float)scale, causal,
+      cur_stream()));
   return {ctx, lse};
 }
 
@@ -1771,7 +1776,7 @@ static std::vector<Tensor> flash_attn_varlen_drop_fwd_b(
 static Tensor flash_attn_varlen_drop_bwd_b(
     const Tensor &qkv, const Tensor &ctx, const Tensor &dctx,
     const Tensor &lse, const Tensor &cu_seqlens, int64_t max_seqlen,
-    double scale, const Tensor &state, double p, int64_t site) {
+    double scale, const Tensor &state, double p, int64_t site, bool causal) {
   const VarlenShape d = check_varlen_qkv(qkv, -1, cu_seqlens, max_seqlen);
   check_varlen_drop_shape(d);
   check_varlen_ctx(ctx, qkv, d, "ctx");
@@ -1786,7 +1791,7 @@ static Tensor flash_attn_varlen_drop_bwd_b(
       qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr<float>(),
       delta.data_ptr<float>(), cu_seqlens.data_ptr<int>(),
       state.data_ptr<int64_t>(), dp.site, dp.thr, dp.scale, dqkv.data_ptr(),
-      d.N, d.T, d.max_seqlen, d.H, (float)scale, cur_stream()));
+      d.N, d.T, d.max_seqlen, d.H, (float)scale, causal, cur_stream()));
   return dqkv;
 }
 
@@ -2366,8 +2371,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_gelu_fwd", &linear_gelu_fwd);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
-  m.def("flash_attn_fwd", &flash_attn_fwd);
-  m.def("flash_attn_bwd", &flash_attn_bwd);
+  // causal (every flash entry point, default false): row i sees keys j <= i
+  m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("qkv"), py::arg("heads"),
+        py::arg("scale"), py::arg("mask"), py::arg("causal") = false);
+  m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("qkv"), py::arg("ctx"),
+        py::arg("dctx"), py::arg("lse"), py::arg("scale"), py::arg("mask"),
+        py::arg("causal") = false);
   m.def("attn_drop_fwd", &attn_drop_fwd_b, py::arg("qkv"), py::arg("heads"),
         py::arg("scale"), py::arg("mask"), py::arg("state"), py::arg("p"),
         py::arg("site"));
@@ -2375,24 +2384,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("signed_probs"), py::arg("scale"), py::arg("p"));
   m.def("flash_attn_drop_fwd", &flash_attn_drop_fwd_b, py::arg("qkv"),
         py::arg("heads"), py::arg("scale"), py::arg("mask"), py::arg("state"),
-        py::arg("p"), py::arg("site"));
+        py::arg("p"), py::arg("site"), py::arg("causal") = false);
   m.def("flash_attn_drop_bwd", &flash_attn_drop_bwd_b, py::arg("qkv"),
         py::arg("ctx"), py::arg("dctx"), py::arg("lse"), py::arg("scale"),
-        py::arg("mask"), py::arg("state"), py::arg("p"), py::arg("site"));
+        py::arg("mask"), py::arg("state"), py::arg("p"), py::arg("site"),
+        py::arg("causal") = false);
   m.def("flash_attn_varlen_fwd", &flash_attn_varlen_fwd, py::arg("qkv"),
         py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("heads"),
-        py::arg("scale"));
+        py::arg("scale"), py::arg("causal") = false);
   m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd, py::arg("qkv"),
         py::arg("ctx"), py::arg("dctx"), py::arg("lse"),
-        py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("scale"));
+        py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("scale"),
+        py::arg("causal") = false);
   m.def("flash_attn_varlen_drop_fwd", &flash_attn_varlen_drop_fwd_b,
         py::arg("qkv"), py::arg("cu_seqlens"), py::arg("max_seqlen"),
         py::arg("heads"), py::arg("scale"), py::arg("state"), py::arg("p"),
-        py::arg("site"));
+        py::arg("site"), py::arg("causal") = false);
   m.def("flash_attn_varlen_drop_bwd", &flash_attn_varlen_drop_bwd_b,
         py::arg("qkv"), py::arg("ctx"), py::arg("dctx"), py::arg("lse"),
         py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("scale"),
-        py::arg("state"), py::arg("p"), py::arg("site"));
+        py::arg("state"), py::arg("p"), py::arg("site"),
+        py::arg("causal") = false);
   m.def("linear_wgrad_only", &linear_wgrad_only);
   m.def("linear_gelu_dgrad", &linear_gelu_dgrad);
   m.def("masked_xent_bwd", &masked_xent_bwd);

@@ -57,6 +57,35 @@
 // Rows at or past cu[N] belong to no block: the launchers zero ctx, lse
 // and dqkv ahead of the kernels (memset nodes under capture).
 // DROP keys the masks per sequence: see philox.h.
+//
+// CAUSAL (third template parameter of the three MFMA kernels): query row i
+// of a sequence sees the keys j <= i of that sequence (positions counted from
+// the sequence start under VARLEN); lse is that of the causal row. Q-chunks
+// and key tiles are both 128 rows and aligned, so the work is a triangle of
+// tiles and only its diagonal needs a per-element decision:
+//   - forward and dQ block (.., c) walk the key tiles kt <= c, dK/dV block
+//     (.., c) the q-chunks qc >= c. Tiles in the future are never staged,
+//     multiplied or drawn for; the bounds depend on blockIdx and S only, so
+//     every barrier stays workgroup-uniform.
+//   - the past tiles run the dense tile body, unchanged and without any
+//     causal test. The one diagonal tile (kt == c, qc == c) has a body of
+//     its own (fa_fwd_diag, fa_dkv_diag, fa_dq_diag, instantiated by the
+//     CAUSAL kernels only): a future column is excluded as a column >= S
+//     is, by selection per (register row, column), floor into the max and
+//     p = 0, which also zeroes dS. Nothing is added to a score. With the
+//     key mask, excluded = future or masked.
+//   - wave w owns rows w·32..+31 of the diagonal tile, so its column
+//     fragments ni > w lie wholly in the future: the forward skips their
+//     QKᵀ MFMAs, their keep draws and the k-steps >= 2(w+1) of P·V. The
+//     decision is wave-uniform (scalar branches on the wave index, EXEC
+//     stays all ones) and indexes registers at compile time. The backward
+//     bodies do not trim: it measured slower there.
+//   - forward and dQ block c does c + 1 tiles, so blockIdx.y is mapped to
+//     chunks last-first (the heaviest blocks are dispatched first); dK/dV
+//     block c does nqc − c and is heaviest-first as it is.
+//   - DROP keep bits are keyed by (row, column), so a causal call draws the
+//     dense call's bits of the lower triangle.
+// A row always sees its own key, so causality alone leaves no empty row.
 #include "common.h"
 #include "launchers.h"
 #include "philox.h"
@@ -71,6 +100,18 @@ constexpr int FA_T = 128;   // q-chunk rows and key-tile width
 // and above finfo(float).min, so a masked score (≈ finfo.min) minus the
 // floor is still hugely negative and its exp is exactly 0
 constexpr float FA_FLOOR = -3.4e38f;
+
+// CAUSAL visibility inside the (aligned, 128×128) diagonal tile. Row r of
+// the C layout sits at chunk offset sqw + fa_crow(r, lane) and column
+// fragment ni holds column ni·32 + (lane & 31), so "column <= row" is
+//   fa_cvis(lane, sqw) <= (r & 3) + 8·(r >> 2) − ni·32:
+// one VGPR against a compile-time constant per (r, ni).
+DEV_INLINE int fa_cvis(int lane, int sqw) {
+  return (lane & 31) - 4 * (lane >> 5) - sqw;
+}
+DEV_INLINE bool fa_cvis_ok(int cv, int r, int ni) {
+  return cv <= (r & 3) + 8 * (r >> 2) - ni * 32;
+}
 
 // launch arguments of the VARLEN kernels (unused where VARLEN is false)
 struct FaVarlen {
@@ -195,10 +236,104 @@ DEV_INLINE float16a fa_nt_frag(const bf16x8a af[4], const ushort8 *img, int ni,
 }
 
 // ------------------------------ forward ------------------------------
+// The diagonal tile of a CAUSAL forward block, K/V images staged by the
+// caller: the dense tile body with the future columns selected away and
+// this wave's all-future fragments (ni >= nfr) and k-steps skipped.
+// p_w: this wave's P image; mrow: the batch row's key mask or nullptr.
+// TWIN of the tile loop body in flash_attn_fwd_k (scores, online softmax,
+// park, P·V), repeated here so the dense kernels never see the causal code:
+// a fix to either must be made in both by hand.
+template <bool DROP>
+DEV_INLINE void fa_fwd_diag(const bf16x8a qf[4], const ushort8 *k_img,
+                            const ushort8 *v_img, uint16_t (*p_w)[FA_T],
+                            const float *mrow, int k0, int S, float scale,
+                            int lane, int wave, int qrow0, const AttnDrop &dr,
+                            float m_run[16], float l_run[16],
+                            float16a oacc[2]) {
+  const int nfr = __builtin_amdgcn_readfirstlane(wave) + 1;
+  const int cv = fa_cvis(lane, wave * 32);
+  float16a acc[4];
+  float mk[4];
+  bool cok[4];
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+    if (ni < nfr)
+      acc[ni] = fa_nt_frag(qf, k_img, ni, lane);
+    else
+      acc[ni] = float16a{};
+    int col = k0 + ni * 32 + (lane & 31);
+    cok[ni] = col < S;
+    mk[ni] = (mrow && cok[ni]) ? mrow[col] : 0.f;
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float mt = FA_FLOOR;
+    bool ok[4];
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      ok[ni] = cok[ni] && fa_cvis_ok(cv, r, ni);
+      float v = ok[ni] ? acc[ni][r] * scale + mk[ni] : FA_FLOOR;
+      acc[ni][r] = v;
+      mt = fmaxf(mt, v);
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1)
+      mt = fmaxf(mt, __shfl_xor(mt, off, 64));
+    float m_new = fmaxf(m_run[r], mt);
+    float alpha = __expf(m_run[r] - m_new);
+    float s = 0.f;
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      float e = ok[ni] ? __expf(acc[ni][r] - m_new) : 0.f;
+      acc[ni][r] = e;
+      s += e;
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1)
+      s += __shfl_xor(s, off, 64);
+    m_run[r] = m_new;
+    l_run[r] = l_run[r] * alpha + s;
+    oacc[0][r] *= alpha;
+    oacc[1][r] *= alpha;
+  }
+  // park P (DROP: e·keep); the fragments ni >= nfr are never read below
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+    if (ni >= nfr) continue;
+    uint32_t kb = 0xffffu;
+    if (DROP)
+      kb = attn_drop_keep16(dr, (uint32_t)qrow0 >> 4, lane >> 5,
+                            k0 + ni * 32 + (lane & 31));
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      uint16_t pv = f2bf(acc[ni][r]);
+      p_w[fa_crow(r, lane)][ni * 32 + (lane & 31)] =
+          ((kb >> r) & 1u) ? pv : (uint16_t)0;
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int ks = 0; ks < FA_T / 16; ++ks) {
+    if (ks >= 2 * nfr) continue; // P is zero from here on
+    int r = lane & 31, kk = ks * 16 + (lane >> 5) * 8;
+    bf16x8a pf = fa_bf8(*(const ushort8 *)&p_w[r][kk]);
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      int kq0 = ks * 4 + ((lane >> 5) & 1) * 2;
+      int cq = ni * 2 + ((lane >> 4) & 1);
+      bf16x8a vf = fa_tr_frag<4>(v_img, kq0, cq, lane);
+      oacc[ni] =
+          __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, vf, oacc[ni], 0, 0, 0);
+    }
+  }
+}
+
 // grid (B·H, ceil(S/128)); LDS K 16 KiB + V 16 KiB + P 32 KiB = 64 KiB
 // (2 workgroups per CU).
 // VARLEN: grid (N·H, ceil(max_seqlen/128)), B = N, S_ unused, no mask.
-template <bool DROP, bool VARLEN = false>
+// CAUSAL: block row y owns chunk yc = gridDim.y − 1 − y: key tiles 0..yc − 1
+// in the dense body, then tile yc in fa_fwd_diag.
+template <bool DROP, bool VARLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
     const uint16_t *__restrict__ qkv, // [B, S, 3, H, 64]
     uint16_t *__restrict__ ctx,       // [B, S, H*64]
@@ -210,8 +345,9 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
   int b = bh / H, h = bh % H;
   const FaSeq sq = fa_seq<VARLEN>(bh, H, S_, vl);
   const int S = sq.S;
+  const int yc = CAUSAL ? gridDim.y - 1 - blockIdx.y : blockIdx.y;
   // workgroup-uniform, ahead of the first barrier
-  if (VARLEN && (int)blockIdx.y * T >= S) return;
+  if (VARLEN && yc * T >= S) return;
   const float *mask = VARLEN ? nullptr : mask_;
   int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
@@ -227,7 +363,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
 
   // A wave whose 32 q-rows are all >= S stays in the loop (zero Q, nothing
   // written): every wave must reach both barriers of every tile.
-  int qrow0 = blockIdx.y * T + wave * 32;
+  int qrow0 = yc * T + wave * 32;
   bf16x8a qf[4];
   fa_load_rows(qf, qp, qkv_row, qrow0, S, lane);
 
@@ -241,7 +377,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
   AttnDrop dr{};
   if (DROP) dr = attn_drop_init(da, bh, VARLEN ? vl.max_seqlen : S);
 
-  const int nkt = (S + T - 1) / T;
+  // CAUSAL: chunk yc exists (yc·T < S), so the tiles 0..yc all do
+  const int nkt = CAUSAL ? yc : (S + T - 1) / T;
   for (int kt = 0; kt < nkt; ++kt) {
     const int k0 = kt * T;
     // first barrier: no wave is still reading the previous tile's K/V
@@ -251,6 +388,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
     fa_stage_tr(v_img, vp, qkv_row, k0, S, tid);
     __syncthreads();
 
+    // (this tile body has a TWIN for the diagonal tile, fa_fwd_diag: mirror
+    // any fix there)
     // scores: compile-time fragment count (runtime-indexed accumulators
     // spill); key columns >= S compute zeros and are excluded below
     float16a acc[4];
@@ -344,6 +483,16 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
       }
     }
   }
+  if constexpr (CAUSAL) {
+    const int k0 = yc * T;
+    __syncthreads();
+    fa_stage_nt(k_img, kp, qkv_row, k0, S, tid);
+    fa_stage_tr(v_img, vp, qkv_row, k0, S, tid);
+    __syncthreads();
+    fa_fwd_diag<DROP>(qf, k_img, v_img, p_img[wave],
+                      mask ? mask + (long)b * S : nullptr, k0, S, scale, lane,
+                      wave, qrow0, dr, m_run, l_run, oacc);
+  }
 
   // ctx = O / l, lse = m + log(l). A row with no valid key at all has
   // l = 0: write zeros and lse = floor (finite) instead of 0/0.
@@ -363,28 +512,39 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_k(
   }
 }
 
+// the forward instantiation for (DROP, VARLEN) and the runtime causal flag
+template <bool DROP, bool VARLEN>
+static hipError_t fa_fwd(const void *qkv, void *ctx, float *lse,
+                         const float *mask, int B, int S, int H, float scale,
+                         AttnDropArgs da, FaVarlen vl, int causal,
+                         hipStream_t strm) {
+  int rows = VARLEN ? vl.max_seqlen : S;
+  dim3 grid(B * H, (rows + FA_T - 1) / FA_T);
+  auto k = causal ? flash_attn_fwd_k<DROP, VARLEN, true>
+                  : flash_attn_fwd_k<DROP, VARLEN, false>;
+  k<<<grid, 256, 0, strm>>>((const uint16_t *)qkv, (uint16_t *)ctx, lse, mask,
+                            B, S, H, scale, da, vl);
+  HIP_KERNEL_CHECK();
+  return hipSuccess;
+}
+
 extern "C" hipError_t flash_attn_fwd_launch(const void *qkv, void *ctx,
                                             float *lse, const float *mask,
                                             int B, int S, int H, float scale,
-                                            hipStream_t strm) {
+                                            int causal, hipStream_t strm) {
   if (S < 1) return hipErrorInvalidValue;
-  flash_attn_fwd_k<false><<<dim3(B * H, (S + FA_T - 1) / FA_T), 256, 0, strm>>>(
-      (const uint16_t *)qkv, (uint16_t *)ctx, lse, mask, B, S, H, scale,
-      AttnDropArgs{}, FaVarlen{});
-  HIP_KERNEL_CHECK();
-  return hipSuccess;
+  return fa_fwd<false, false>(qkv, ctx, lse, mask, B, S, H, scale,
+                              AttnDropArgs{}, FaVarlen{}, causal, strm);
 }
 
 extern "C" hipError_t flash_attn_drop_fwd_launch(
     const void *qkv, void *ctx, float *lse, const float *mask,
     const int64_t *state, uint32_t site, uint32_t thr, float rs, int B, int S,
-    int H, float scale, hipStream_t strm) {
+    int H, float scale, int causal, hipStream_t strm) {
   if (S < 1 || !state) return hipErrorInvalidValue;
-  flash_attn_fwd_k<true><<<dim3(B * H, (S + FA_T - 1) / FA_T), 256, 0, strm>>>(
-      (const uint16_t *)qkv, (uint16_t *)ctx, lse, mask, B, S, H, scale,
-      AttnDropArgs{state, site, thr, rs}, FaVarlen{});
-  HIP_KERNEL_CHECK();
-  return hipSuccess;
+  return fa_fwd<true, false>(qkv, ctx, lse, mask, B, S, H, scale,
+                             AttnDropArgs{state, site, thr, rs}, FaVarlen{},
+                             causal, strm);
 }
 
 // Packed forward: zero ctx and lse (the rows past cu[N] stay zero), then one
@@ -393,36 +553,32 @@ template <bool DROP>
 static hipError_t fa_varlen_fwd(const void *qkv, void *ctx, float *lse,
                                 const int *cu_seqlens, AttnDropArgs da, int N,
                                 int T, int max_seqlen, int H, float scale,
-                                hipStream_t strm) {
+                                int causal, hipStream_t strm) {
   if (N < 1 || T < 1 || max_seqlen < 1 || H < 1 || !cu_seqlens)
     return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(ctx, 0, (size_t)T * H * FA_D * 2, strm);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(lse, 0, (size_t)T * H * sizeof(float), strm);
   if (e != hipSuccess) return e;
-  dim3 grid(N * H, (max_seqlen + FA_T - 1) / FA_T);
-  flash_attn_fwd_k<DROP, true><<<grid, 256, 0, strm>>>(
-      (const uint16_t *)qkv, (uint16_t *)ctx, lse, nullptr, N, 0, H, scale, da,
-      FaVarlen{cu_seqlens, T, max_seqlen});
-  HIP_KERNEL_CHECK();
-  return hipSuccess;
+  return fa_fwd<DROP, true>(qkv, ctx, lse, nullptr, N, 0, H, scale, da,
+                            FaVarlen{cu_seqlens, T, max_seqlen}, causal, strm);
 }
 
 extern "C" hipError_t flash_attn_varlen_fwd_launch(
     const void *qkv, void *ctx, float *lse, const int *cu_seqlens, int N, int T,
-    int max_seqlen, int H, float scale, hipStream_t strm) {
+    int max_seqlen, int H, float scale, int causal, hipStream_t strm) {
   return fa_varlen_fwd<false>(qkv, ctx, lse, cu_seqlens, AttnDropArgs{}, N, T,
-                              max_seqlen, H, scale, strm);
+                              max_seqlen, H, scale, causal, strm);
 }
 
 extern "C" hipError_t flash_attn_varlen_drop_fwd_launch(
     const void *qkv, void *ctx, float *lse, const int *cu_seqlens,
     const int64_t *state, uint32_t site, uint32_t thr, float rs, int N, int T,
-    int max_seqlen, int H, float scale, hipStream_t strm) {
+    int max_seqlen, int H, float scale, int causal, hipStream_t strm) {
   if (!state) return hipErrorInvalidValue;
   return fa_varlen_fwd<true>(qkv, ctx, lse, cu_seqlens,
                              AttnDropArgs{state, site, thr, rs}, N, T,
-                             max_seqlen, H, scale, strm);
+                             max_seqlen, H, scale, causal, strm);
 }
 
 // ------------------------------ backward ------------------------------
@@ -464,14 +620,16 @@ __global__ __launch_bounds__(256) void flash_attn_delta_k(
 // 16 row predicates then need not stay live in SGPR pairs across the call
 // (the VARLEN dK/dV kernel spilled SGPRs without it). Valid rows are
 // computed exactly as with ROWINF = false.
-template <bool DROP, bool ROWINF = false>
+// DIAG (the diagonal tile of a CAUSAL kernel): the keys in the future of a
+// q-row get p = 0, hence dS = 0, too; cv = fa_cvis(lane, sqw).
+template <bool DROP, bool ROWINF = false, bool DIAG = false>
 DEV_INLINE void fa_pds_frag(const bf16x8a qf[4], const bf16x8a dof[4],
                             const ushort8 *k_nt, const ushort8 *v_nt, int ni,
                             int lane, int sqw, bool cok, float mk,
                             const float lse_r[16], const float delta_r[16],
                             const bool rok[16], float scale, uint16_t *p16,
                             uint16_t *ds16, const AttnDrop &dr, uint32_t band0,
-                            uint32_t gcol) {
+                            uint32_t gcol, int cv = 0) {
   float16a s = fa_nt_frag(qf, k_nt, ni, lane);
   float16a dp = fa_nt_frag(dof, v_nt, ni, lane);
   int col = ni * 32 + (lane & 31);
@@ -480,7 +638,7 @@ DEV_INLINE void fa_pds_frag(const bf16x8a qf[4], const bf16x8a dof[4],
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     int row = sqw + fa_crow(r, lane);
-    float p = (cok && (ROWINF || rok[r]))
+    float p = (cok && (ROWINF || rok[r]) && (!DIAG || fa_cvis_ok(cv, r, ni)))
                   ? __expf(s[r] * scale + mk - lse_r[r]) : 0.f;
     float dpe = dp[r], pk = p;
     if (DROP) {
@@ -495,11 +653,55 @@ DEV_INLINE void fa_pds_frag(const bf16x8a qf[4], const bf16x8a dof[4],
   }
 }
 
+// The diagonal q-chunk (qc == key chunk) of a CAUSAL dK/dV block, Q/dO
+// images staged by the caller: the dense chunk body with the future keys
+// of each q-row selected away. No wave-uniform trim here or in fa_dq_diag:
+// skipping the all-future fragments and their k-steps measured 2 % slower
+// on the whole backward (profiles/BENCH_HISTORY.md).
+// TWIN of the recompute + accumulate part of the q-chunk loop body in
+// flash_attn_bwd_dkv_k; that kernel's CAUSAL prologue also repeats the
+// loop's staging and lse/delta row loads. Mirror a fix to one in the other.
+template <bool DROP, bool ROWINF>
+DEV_INLINE void fa_dkv_diag(const bf16x8a qf[4], const bf16x8a dof[4],
+                            const ushort8 *k_nt, const ushort8 *v_nt,
+                            const ushort8 *q_tr, const ushort8 *do_tr,
+                            ushort8 *p_tr, ushort8 *ds_tr, int lane, int wave,
+                            const bool cok[4], const float mk[4],
+                            const float lse_r[16], const float delta_r[16],
+                            const bool rok[16], float scale,
+                            const AttnDrop &dr, int kc0, float16a dk[2],
+                            float16a dv[2]) {
+  const int sqw = wave * 32, cv = fa_cvis(lane, sqw);
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+    fa_pds_frag<DROP, ROWINF, true>(
+        qf, dof, k_nt, v_nt, ni, lane, sqw, cok[ni], mk[ni], lse_r, delta_r,
+        rok, scale, (uint16_t *)p_tr, (uint16_t *)ds_tr, dr,
+        (uint32_t)(kc0 + sqw) >> 4, kc0 + ni * 32 + (lane & 31), cv);
+  }
+  __syncthreads();
+  for (int ks = 0; ks < 8; ++ks) {
+    int kq0 = ks * 4 + ((lane >> 5) & 1) * 2;
+    int cqa = (sqw >> 4) + ((lane >> 4) & 1);
+    bf16x8a a_ds = fa_tr_frag<8>(ds_tr, kq0, cqa, lane);
+    bf16x8a a_p = fa_tr_frag<8>(p_tr, kq0, cqa, lane);
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      int cq = ni * 2 + ((lane >> 4) & 1);
+      bf16x8a b_q = fa_tr_frag<4>(q_tr, kq0, cq, lane);
+      bf16x8a b_do = fa_tr_frag<4>(do_tr, kq0, cq, lane);
+      dk[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_ds, b_q, dk[ni], 0, 0, 0);
+      dv[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_p, b_do, dv[ni], 0, 0, 0);
+    }
+  }
+}
+
 // dK, dV: grid (B·H, ceil(S/128)) over key chunks, loop over q-chunks.
 // LDS: K, V (NT, staged once) + Q, dO (subtile, per q-chunk) 4×16 KiB
 // + P, dS 2×32 KiB = 128 KiB.
 // VARLEN: grid (N·H, ceil(max_seqlen/128)), B = N, S_ unused, no mask.
-template <bool DROP, bool VARLEN = false>
+// CAUSAL: q-chunk blockIdx.y in fa_dkv_diag, then the later ones as dense.
+template <bool DROP, bool VARLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
     const uint16_t *__restrict__ qkv,   // [B, S, 3, H, 64]
     const uint16_t *__restrict__ dctx,  // [B, S, H*64]
@@ -514,6 +716,9 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
   const FaSeq sq = fa_seq<VARLEN>(bh, H, S_, vl);
   const int S = sq.S;
   const int kc0 = blockIdx.y * T;
+  // fa_pds_frag's ROWINF: the CAUSAL kernels take it too (their DROP forms
+  // spilled SGPRs on the 16 row predicates)
+  constexpr bool RI = VARLEN || CAUSAL;
   // workgroup-uniform, ahead of the first barrier
   if (VARLEN && kc0 >= S) return;
   const float *mask = VARLEN ? nullptr : mask_;
@@ -553,7 +758,29 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
   AttnDrop dr{};
   if (DROP) dr = attn_drop_init(da, bh, VARLEN ? vl.max_seqlen : S);
   const int nqc = (S + T - 1) / T;
-  for (int qc = 0; qc < nqc; ++qc) {
+  if constexpr (CAUSAL) {
+    // the diagonal chunk: the head of the loop body below, repeated (TWIN)
+    __syncthreads();
+    fa_stage_tr(q_tr, qp, qrow, kc0, S, tid);
+    fa_stage_tr(do_tr, dop, crow, kc0, S, tid);
+    __syncthreads();
+    bf16x8a qf[4], dof[4];
+    fa_load_rows(qf, qp, qrow, kc0 + sqw, S, lane);
+    fa_load_rows(dof, dop, crow, kc0 + sqw, S, lane);
+    float lse_r[16], delta_r[16];
+    bool rok[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      int row = kc0 + sqw + fa_crow(r, lane);
+      rok[r] = row < S;
+      lse_r[r] = rok[r] ? lsep[row] : (RI ? INFINITY : 0.f);
+      delta_r[r] = rok[r] ? delp[row] : 0.f;
+    }
+    fa_dkv_diag<DROP, RI>(qf, dof, k_nt, v_nt, q_tr, do_tr, p_tr, ds_tr,
+                              lane, wave, cok, mk, lse_r, delta_r, rok, scale,
+                              dr, kc0, dk, dv);
+  }
+  for (int qc = CAUSAL ? (int)blockIdx.y + 1 : 0; qc < nqc; ++qc) {
     const int q0 = qc * T;
     // first barrier: the previous chunk's dK/dV reads of all four per-chunk
     // images are done; second: Q/dO (and, first time, K/V) are staged
@@ -572,18 +799,20 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
       int row = q0 + sqw + fa_crow(r, lane);
       rok[r] = row < S;
       // VARLEN: rows >= S get P = exp(0 − inf) = 0 (fa_pds_frag ROWINF)
-      lse_r[r] = rok[r] ? lsep[row] : (VARLEN ? INFINITY : 0.f);
+      lse_r[r] = rok[r] ? lsep[row] : (RI ? INFINITY : 0.f);
       delta_r[r] = rok[r] ? delp[row] : 0.f;
     }
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni)
-      fa_pds_frag<DROP, VARLEN>(
+      fa_pds_frag<DROP, RI>(
           qf, dof, k_nt, v_nt, ni, lane, sqw, cok[ni], mk[ni], lse_r, delta_r,
           rok, scale, (uint16_t *)p_tr, (uint16_t *)ds_tr, dr,
           (uint32_t)(q0 + sqw) >> 4, kc0 + ni * 32 + (lane & 31));
     __syncthreads();
 
     // dK += dSᵀ·Q, dV += Pᵀ·dO: rows = this wave's 32 keys, k = the 128 q
+    // (this chunk body has a TWIN, fa_dkv_diag and the CAUSAL prologue
+    // above: mirror any fix there)
     for (int ks = 0; ks < 8; ++ks) {
       int kq0 = ks * 4 + ((lane >> 5) & 1) * 2;
       int cqa = (sqw >> 4) + ((lane >> 4) & 1);
@@ -615,13 +844,53 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dkv_k(
   }
 }
 
+// The diagonal key tile of a CAUSAL dQ block, K/V images staged by the
+// caller. TWIN of the key-tile loop body in flash_attn_bwd_dq_k (recompute
+// dS, dQ += dS·K): a fix to either must be made in both by hand.
+template <bool DROP, bool ROWINF>
+DEV_INLINE void fa_dq_diag(const bf16x8a qf[4], const bf16x8a dof[4],
+                           const ushort8 *k_nt, const ushort8 *v_nt,
+                           const ushort8 *k_tr, ushort8 *ds_tr,
+                           const float *mrow, int k0, int S, int lane,
+                           int wave, const float lse_r[16],
+                           const float delta_r[16], const bool rok[16],
+                           float scale, const AttnDrop &dr, float16a dq[2]) {
+  const int sqw = wave * 32, cv = fa_cvis(lane, sqw);
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+    int col = k0 + ni * 32 + (lane & 31);
+    bool cok = col < S;
+    float mk = (mrow && cok) ? mrow[col] : 0.f;
+    fa_pds_frag<DROP, ROWINF, true>(qf, dof, k_nt, v_nt, ni, lane, sqw, cok, mk,
+                                   lse_r, delta_r, rok, scale, nullptr,
+                                   (uint16_t *)ds_tr, dr,
+                                   (uint32_t)(k0 + sqw) >> 4, col, cv);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  for (int ks = 0; ks < 8; ++ks) {
+    int sq = sqw + (lane & 31);
+    int kk = ks * 16 + (lane >> 5) * 8;
+    bf16x8a af = fa_bf8(
+        *(const ushort8 *)((const uint16_t *)ds_tr + fa_sub128(sq, kk)));
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      int kq0 = ks * 4 + ((lane >> 5) & 1) * 2;
+      int cq = ni * 2 + ((lane >> 4) & 1);
+      bf16x8a bf = fa_tr_frag<4>(k_tr, kq0, cq, lane);
+      dq[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, dq[ni], 0, 0, 0);
+    }
+  }
+}
+
 // dQ: grid (B·H, ceil(S/128)) over q-chunks, loop over key tiles.
 // LDS: K, V (NT) + K (subtile) 3×16 KiB + dS 32 KiB = 80 KiB. The dS image
 // is written and read by the same wave (its own 32 q-rows = 8 private row
 // blocks), so it needs a wave-level fence only.
 // VARLEN: grid (N·H, ceil(max_seqlen/128)), B = N, S_ unused, no mask.
-template <bool DROP, bool VARLEN = false>
-__global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
+// CAUSAL: chunk yc as in the forward; key tiles 0..yc − 1 as dense, then
+// tile yc in fa_dq_diag.
+template <bool DROP, bool VARLEN = false, bool CAUSAL = false>
+__global__ __launch_bounds__(256, CAUSAL ? 2 : 1) void flash_attn_bwd_dq_k(
     const uint16_t *__restrict__ qkv, const uint16_t *__restrict__ dctx,
     const float *__restrict__ lse, const float *__restrict__ delta,
     const float *__restrict__ mask_, uint16_t *__restrict__ dqkv, int B,
@@ -631,7 +900,11 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
   int b = bh / H, h = bh % H;
   const FaSeq sq = fa_seq<VARLEN>(bh, H, S_, vl);
   const int S = sq.S;
-  const int q0 = blockIdx.y * T;
+  const int yc = CAUSAL ? gridDim.y - 1 - blockIdx.y : blockIdx.y;
+  const int q0 = yc * T;
+  // fa_pds_frag's ROWINF for the CAUSAL DROP forms, which spilled SGPRs on
+  // the row predicates (the others spilled a VGPR with it)
+  constexpr bool RI = CAUSAL && DROP;
   // workgroup-uniform, ahead of the first barrier
   if (VARLEN && q0 >= S) return;
   const float *mask = VARLEN ? nullptr : mask_;
@@ -661,14 +934,14 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
   for (int r = 0; r < 16; ++r) {
     int row = q0 + sqw + fa_crow(r, lane);
     rok[r] = row < S;
-    lse_r[r] = rok[r] ? lsep[row] : 0.f;
+    lse_r[r] = rok[r] ? lsep[row] : (RI ? INFINITY : 0.f);
     delta_r[r] = rok[r] ? delp[row] : 0.f;
   }
 
   float16a dq[2] = {};
   AttnDrop dr{};
   if (DROP) dr = attn_drop_init(da, bh, VARLEN ? vl.max_seqlen : S);
-  const int nkt = (S + T - 1) / T;
+  const int nkt = CAUSAL ? yc : (S + T - 1) / T;
   for (int kt = 0; kt < nkt; ++kt) {
     const int k0 = kt * T;
     __syncthreads(); // previous tile's K/V readers done
@@ -682,13 +955,14 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
       int col = k0 + ni * 32 + (lane & 31);
       bool cok = col < S;
       float mk = (mask && cok) ? mask[(long)b * S + col] : 0.f;
-      fa_pds_frag<DROP>(qf, dof, k_nt, v_nt, ni, lane, sqw, cok, mk, lse_r,
+      fa_pds_frag<DROP, RI>(qf, dof, k_nt, v_nt, ni, lane, sqw, cok, mk, lse_r,
                         delta_r, rok, scale, nullptr, (uint16_t *)ds_tr, dr,
                         (uint32_t)(q0 + sqw) >> 4, col);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
     // dQ += dS·K: A = dS (k-contiguous b128 at subtile-linear addresses)
+    // (this tile body has a TWIN for the diagonal tile, fa_dq_diag)
     for (int ks = 0; ks < 8; ++ks) {
       int sq = sqw + (lane & 31);
       int kk = ks * 16 + (lane >> 5) * 8;
@@ -703,6 +977,16 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
       }
     }
   }
+  if constexpr (CAUSAL) {
+    __syncthreads();
+    fa_stage_nt(k_nt, kp, qrow, q0, S, tid);
+    fa_stage_nt(v_nt, vp, qrow, q0, S, tid);
+    fa_stage_tr(k_tr, kp, qrow, q0, S, tid);
+    __syncthreads();
+    fa_dq_diag<DROP, RI>(qf, dof, k_nt, v_nt, k_tr, ds_tr,
+                     mask ? mask + (long)b * S : nullptr, q0, S, lane, wave,
+                     lse_r, delta_r, rok, scale, dr, dq);
+  }
 
   uint16_t *dq_out = dqkv + sq.tok0 * qrow + h * D;
 #pragma unroll
@@ -715,25 +999,49 @@ __global__ __launch_bounds__(256) void flash_attn_bwd_dq_k(
   }
 }
 
-extern "C" hipError_t flash_attn_bwd_launch(
-    const void *qkv, const void *ctx, const void *dctx, const float *lse,
-    float *delta, const float *mask, void *dqkv, int B, int S, int H,
-    float scale, hipStream_t strm) {
-  if (S < 1) return hipErrorInvalidValue;
+// the dK/dV and dQ instantiations for (DROP, VARLEN) and the
+// runtime causal flag.
+template <bool DROP, bool VARLEN>
+static hipError_t fa_bwd(const void *qkv, const void *dctx, const float *lse,
+                         float *delta, const float *mask,
+                         void *dqkv, int B, int S, int H, float scale,
+                         AttnDropArgs da, FaVarlen vl, int causal,
+                         hipStream_t strm) {
+  int rows = VARLEN ? vl.max_seqlen : S;
+  dim3 grid(B * H, (rows + FA_T - 1) / FA_T);
+  auto dkv = causal ? flash_attn_bwd_dkv_k<DROP, VARLEN, true>
+                    : flash_attn_bwd_dkv_k<DROP, VARLEN, false>;
+  dkv<<<grid, 256, 0, strm>>>((const uint16_t *)qkv, (const uint16_t *)dctx,
+                              lse, delta, mask, (uint16_t *)dqkv, B, S, H,
+                              scale, da, vl);
+  HIP_KERNEL_CHECK();
+  auto dq = causal ? flash_attn_bwd_dq_k<DROP, VARLEN, true>
+                   : flash_attn_bwd_dq_k<DROP, VARLEN, false>;
+  dq<<<grid, 256, 0, strm>>>((const uint16_t *)qkv, (const uint16_t *)dctx,
+                             lse, delta, mask, (uint16_t *)dqkv, B, S, H,
+                             scale, da, vl);
+  HIP_KERNEL_CHECK();
+  return hipSuccess;
+}
+
+static hipError_t fa_delta(const void *ctx, const void *dctx, float *delta,
+                           int B, int S, int H, hipStream_t strm) {
   long nthr = (long)B * S * H * 8;
   flash_attn_delta_k<<<cdiv_h(nthr, 256), 256, 0, strm>>>(
       (const uint16_t *)ctx, (const uint16_t *)dctx, delta, B, S, H);
   HIP_KERNEL_CHECK();
-  dim3 grid(B * H, (S + FA_T - 1) / FA_T);
-  flash_attn_bwd_dkv_k<false><<<grid, 256, 0, strm>>>(
-      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale, AttnDropArgs{}, FaVarlen{});
-  HIP_KERNEL_CHECK();
-  flash_attn_bwd_dq_k<false><<<grid, 256, 0, strm>>>(
-      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale, AttnDropArgs{}, FaVarlen{});
-  HIP_KERNEL_CHECK();
   return hipSuccess;
+}
+
+extern "C" hipError_t flash_attn_bwd_launch(
+    const void *qkv, const void *ctx, const void *dctx, const float *lse,
+    float *delta, const float *mask, void *dqkv, int B, int S, int H,
+    float scale, int causal, hipStream_t strm) {
+  if (S < 1) return hipErrorInvalidValue;
+  hipError_t e = fa_delta(ctx, dctx, delta, B, S, H, strm);
+  if (e != hipSuccess) return e;
+  return fa_bwd<false, false>(qkv, dctx, lse, delta, mask, dqkv, B, S, H,
+                              scale, AttnDropArgs{}, FaVarlen{}, causal, strm);
 }
 
 // state, site, thr, rs: those of the forward; the masks are drawn again
@@ -741,23 +1049,13 @@ extern "C" hipError_t flash_attn_drop_bwd_launch(
     const void *qkv, const void *ctx, const void *dctx, const float *lse,
     float *delta, const float *mask, const int64_t *state, uint32_t site,
     uint32_t thr, float rs, void *dqkv, int B, int S, int H, float scale,
-    hipStream_t strm) {
+    int causal, hipStream_t strm) {
   if (S < 1 || !state) return hipErrorInvalidValue;
-  long nthr = (long)B * S * H * 8;
-  flash_attn_delta_k<<<cdiv_h(nthr, 256), 256, 0, strm>>>(
-      (const uint16_t *)ctx, (const uint16_t *)dctx, delta, B, S, H);
-  HIP_KERNEL_CHECK();
-  dim3 grid(B * H, (S + FA_T - 1) / FA_T);
-  AttnDropArgs da{state, site, thr, rs};
-  flash_attn_bwd_dkv_k<true><<<grid, 256, 0, strm>>>(
-      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale, da, FaVarlen{});
-  HIP_KERNEL_CHECK();
-  flash_attn_bwd_dq_k<true><<<grid, 256, 0, strm>>>(
-      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, mask,
-      (uint16_t *)dqkv, B, S, H, scale, da, FaVarlen{});
-  HIP_KERNEL_CHECK();
-  return hipSuccess;
+  hipError_t e = fa_delta(ctx, dctx, delta, B, S, H, strm);
+  if (e != hipSuccess) return e;
+  return fa_bwd<true, false>(qkv, dctx, lse, delta, mask, dqkv, B, S, H,
+                             scale, AttnDropArgs{state, site, thr, rs},
+                             FaVarlen{}, causal, strm);
 }
 
 // Packed backward: delta over all T rows (the dense kernel at B = 1, S = T;
@@ -768,36 +1066,26 @@ static hipError_t fa_varlen_bwd(const void *qkv, const void *ctx,
                                 const void *dctx, const float *lse,
                                 float *delta, const int *cu_seqlens,
                                 AttnDropArgs da, void *dqkv, int N, int T,
-                                int max_seqlen, int H, float scale,
+                                int max_seqlen, int H, float scale, int causal,
                                 hipStream_t strm) {
   if (N < 1 || T < 1 || max_seqlen < 1 || H < 1 || !cu_seqlens)
     return hipErrorInvalidValue;
-  long nthr = (long)T * H * 8;
-  flash_attn_delta_k<<<cdiv_h(nthr, 256), 256, 0, strm>>>(
-      (const uint16_t *)ctx, (const uint16_t *)dctx, delta, 1, T, H);
-  HIP_KERNEL_CHECK();
-  hipError_t e = hipMemsetAsync(dqkv, 0, (size_t)T * 3 * H * FA_D * 2, strm);
+  hipError_t e = fa_delta(ctx, dctx, delta, 1, T, H, strm);
   if (e != hipSuccess) return e;
-  dim3 grid(N * H, (max_seqlen + FA_T - 1) / FA_T);
-  FaVarlen vl{cu_seqlens, T, max_seqlen};
-  flash_attn_bwd_dkv_k<DROP, true><<<grid, 256, 0, strm>>>(
-      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, nullptr,
-      (uint16_t *)dqkv, N, 0, H, scale, da, vl);
-  HIP_KERNEL_CHECK();
-  flash_attn_bwd_dq_k<DROP, true><<<grid, 256, 0, strm>>>(
-      (const uint16_t *)qkv, (const uint16_t *)dctx, lse, delta, nullptr,
-      (uint16_t *)dqkv, N, 0, H, scale, da, vl);
-  HIP_KERNEL_CHECK();
-  return hipSuccess;
+  e = hipMemsetAsync(dqkv, 0, (size_t)T * 3 * H * FA_D * 2, strm);
+  if (e != hipSuccess) return e;
+  return fa_bwd<DROP, true>(qkv, dctx, lse, delta, nullptr, dqkv, N, 0, H,
+                            scale, da, FaVarlen{cu_seqlens, T, max_seqlen},
+                            causal, strm);
 }
 
 extern "C" hipError_t flash_attn_varlen_bwd_launch(
     const void *qkv, const void *ctx, const void *dctx, const float *lse,
     float *delta, const int *cu_seqlens, void *dqkv, int N, int T,
-    int max_seqlen, int H, float scale, hipStream_t strm) {
+    int max_seqlen, int H, float scale, int causal, hipStream_t strm) {
   return fa_varlen_bwd<false>(qkv, ctx, dctx, lse, delta, cu_seqlens,
                               AttnDropArgs{}, dqkv, N, T, max_seqlen, H, scale,
-                              strm);
+                              causal, strm);
 }
 
 // state, site, thr, rs: those of the forward; the masks are drawn again
@@ -805,9 +1093,9 @@ extern "C" hipError_t flash_attn_varlen_drop_bwd_launch(
     const void *qkv, const void *ctx, const void *dctx, const float *lse,
     float *delta, const int *cu_seqlens, const int64_t *state, uint32_t site,
     uint32_t thr, float rs, void *dqkv, int N, int T, int max_seqlen, int H,
-    float scale, hipStream_t strm) {
+    float scale, int causal, hipStream_t strm) {
   if (!state) return hipErrorInvalidValue;
   return fa_varlen_bwd<true>(qkv, ctx, dctx, lse, delta, cu_seqlens,
                              AttnDropArgs{state, site, thr, rs}, dqkv, N, T,
-                             max_seqlen, H, scale, strm);
+                             max_seqlen, H, scale, causal, strm);
 }

@@ -190,13 +190,15 @@ hipError_t attn_drop_bwd_launch(const void *qkv, const void *dctx,
                                 int S, int H, float scale, hipStream_t strm);
 
 // ---- flash_attention.hip ----
+// causal != 0 (every entry point): row i sees the keys j <= i of its own
+// sequence; the CAUSAL instantiations, which skip the future tiles.
 hipError_t flash_attn_fwd_launch(const void *qkv, void *ctx, float *lse,
                                  const float *mask, int B, int S, int H,
-                                 float scale, hipStream_t strm);
+                                 float scale, int causal, hipStream_t strm);
 hipError_t flash_attn_bwd_launch(const void *qkv, const void *ctx,
                                  const void *dctx, const float *lse,
                                  float *delta, const float *mask, void *dqkv,
-                                 int B, int S, int H, float scale,
+                                 int B, int S, int H, float scale, int causal,
                                  hipStream_t strm);
 // the same with dropout on P; the backward draws the forward's masks again
 // from the same (state, site), so state must hold what the forward read
@@ -204,14 +206,14 @@ hipError_t flash_attn_drop_fwd_launch(const void *qkv, void *ctx, float *lse,
                                       const float *mask, const int64_t *state,
                                       uint32_t site, uint32_t thr, float rs,
                                       int B, int S, int H, float scale,
-                                      hipStream_t strm);
+                                      int causal, hipStream_t strm);
 hipError_t flash_attn_drop_bwd_launch(const void *qkv, const void *ctx,
                                       const void *dctx, const float *lse,
                                       float *delta, const float *mask,
                                       const int64_t *state, uint32_t site,
                                       uint32_t thr, float rs, void *dqkv,
                                       int B, int S, int H, float scale,
-                                      hipStream_t strm);
+                                      int causal, hipStream_t strm);
 // packed ("varlen") forms: N sequence slots back to back in T-row buffers,
 // qkv/dqkv [T,3,H,64], ctx/dctx [T,H*64], lse/delta [H,T], cu_seqlens device
 // int32 [N+1] (cu[0] = 0, non-decreasing, cu[N] <= T, no length above
@@ -220,24 +222,24 @@ hipError_t flash_attn_drop_bwd_launch(const void *qkv, const void *ctx,
 hipError_t flash_attn_varlen_fwd_launch(const void *qkv, void *ctx, float *lse,
                                         const int *cu_seqlens, int N, int T,
                                         int max_seqlen, int H, float scale,
-                                        hipStream_t strm);
+                                        int causal, hipStream_t strm);
 hipError_t flash_attn_varlen_bwd_launch(const void *qkv, const void *ctx,
                                         const void *dctx, const float *lse,
                                         float *delta, const int *cu_seqlens,
                                         void *dqkv, int N, int T,
                                         int max_seqlen, int H, float scale,
-                                        hipStream_t strm);
+                                        int causal, hipStream_t strm);
 // with dropout on P: sequence n draws the masks of batch row n of a dense
 // [N, max_seqlen] batch (philox.h)
 hipError_t flash_attn_varlen_drop_fwd_launch(
     const void *qkv, void *ctx, float *lse, const int *cu_seqlens,
     const int64_t *state, uint32_t site, uint32_t thr, float rs, int N, int T,
-    int max_seqlen, int H, float scale, hipStream_t strm);
+    int max_seqlen, int H, float scale, int causal, hipStream_t strm);
 hipError_t flash_attn_varlen_drop_bwd_launch(
     const void *qkv, const void *ctx, const void *dctx, const float *lse,
     float *delta, const int *cu_seqlens, const int64_t *state, uint32_t site,
     uint32_t thr, float rs, void *dqkv, int N, int T, int max_seqlen, int H,
-    float scale, hipStream_t strm);
+    float scale, int causal, hipStream_t strm);
 
 // ---- gemm.hip ----
 hipError_t gemm_nt(const void *a, const void *b, void *c, int M, int N, int K,

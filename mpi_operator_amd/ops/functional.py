@@ -619,14 +619,16 @@ class FlashAttentionFn(torch.autograd.Function):
     qkv: [B, S, 3, H, 64] → ctx [B, S, H·64]."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, scale, mask):
+    def forward(ctx, qkv, heads, scale, mask, causal=False):
         qkv = qkv.contiguous()
         if qkv.is_cuda and qkv.dtype == torch.bfloat16:
-            out, lse = hip_ext().flash_attn_fwd(qkv, heads, scale, mask)
+            out, lse = hip_ext().flash_attn_fwd(qkv, heads, scale, mask,
+                                                causal)
         else:
-            out, lse = ref.flash_attention_fwd(qkv, heads, scale, mask)
+            out, lse = ref.flash_attention_fwd(qkv, heads, scale, mask,
+                                               causal=causal)
         ctx.save_for_backward(qkv, out, lse, mask)
-        ctx.scale = scale
+        ctx.scale, ctx.causal = scale, causal
         return out
 
     @staticmethod
@@ -634,11 +636,11 @@ class FlashAttentionFn(torch.autograd.Function):
         qkv, out, lse, mask = ctx.saved_tensors
         if qkv.is_cuda and qkv.dtype == torch.bfloat16:
             dqkv = hip_ext().flash_attn_bwd(qkv, out, dout.contiguous(), lse,
-                                            ctx.scale, mask)
+                                            ctx.scale, mask, ctx.causal)
         else:
             dqkv = ref.flash_attention_bwd(qkv, out, dout, lse, ctx.scale,
-                                           mask)
-        return dqkv, None, None, None
+                                           mask, causal=ctx.causal)
+        return dqkv, None, None, None, None
 
 
 class FlashAttentionDropFn(torch.autograd.Function):
@@ -649,13 +651,13 @@ class FlashAttentionDropFn(torch.autograd.Function):
     cannot desynchronise the two."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, scale, mask, p, state, site):
+    def forward(ctx, qkv, heads, scale, mask, p, state, site, causal=False):
         qkv = qkv.contiguous()
         state = state.clone()
         out, lse = hip_ext().flash_attn_drop_fwd(qkv, heads, scale, mask,
-                                                 state, p, site)
+                                                 state, p, site, causal)
         ctx.save_for_backward(qkv, out, lse, mask, state)
-        ctx.scale, ctx.p, ctx.site = scale, p, site
+        ctx.scale, ctx.p, ctx.site, ctx.causal = scale, p, site, causal
         return out
 
     @staticmethod
@@ -663,12 +665,12 @@ class FlashAttentionDropFn(torch.autograd.Function):
         qkv, out, lse, mask, state = ctx.saved_tensors
         dqkv = hip_ext().flash_attn_drop_bwd(qkv, out, dout.contiguous(), lse,
                                              ctx.scale, mask, state, ctx.p,
-                                             ctx.site)
-        return (dqkv,) + (None,) * 6
+                                             ctx.site, ctx.causal)
+        return (dqkv,) + (None,) * 7
 
 
 def flash_attention(qkv, heads, scale, mask=None, p: float = 0.0, rng=None,
-                    site: int = 0):
+                    site: int = 0, causal: bool = False):
     """softmax(Q·Kᵀ·scale + mask)·V for qkv [B, S, 3, H, 64] → [B, S, H·64].
 
     mask: optional additive key mask [B, S] (0 = keep, a large negative
@@ -677,12 +679,16 @@ def flash_attention(qkv, heads, scale, mask=None, p: float = 0.0, rng=None,
     A batch row with NO valid key is outside the contract: its output and
     gradients are only guaranteed to be finite.
     p > 0 (GPU bf16 only) drops out the softmax output with masks from
-    `rng` at call site `site`; p == 0 is the dropout-free path itself."""
+    `rng` at call site `site`; p == 0 is the dropout-free path itself.
+    causal: query row i sees the keys j <= i only (autoregressive); the HIP
+    kernels then skip the key tiles in the future instead of masking them.
+    It combines with `mask` (a key is dropped if it is masked or in the
+    future) and with dropout, whose keep bits are the non-causal call's."""
     if p == 0:
-        return FlashAttentionFn.apply(qkv, heads, scale, mask)
+        return FlashAttentionFn.apply(qkv, heads, scale, mask, causal)
     _check_attn_dropout(qkv, p, rng)
     return FlashAttentionDropFn.apply(qkv, heads, scale, mask, p, rng.state,
-                                      site)
+                                      site, causal)
 
 
 class FlashAttentionVarlenFn(torch.autograd.Function):
@@ -694,16 +700,16 @@ class FlashAttentionVarlenFn(torch.autograd.Function):
     → ctx [T, H·64]."""
 
     @staticmethod
-    def forward(ctx, qkv, cu_seqlens, max_seqlen, heads, scale):
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, heads, scale, causal=False):
         qkv = qkv.contiguous()
         if qkv.is_cuda and qkv.dtype == torch.bfloat16:
-            out, lse = hip_ext().flash_attn_varlen_fwd(qkv, cu_seqlens,
-                                                       max_seqlen, heads, scale)
+            out, lse = hip_ext().flash_attn_varlen_fwd(
+                qkv, cu_seqlens, max_seqlen, heads, scale, causal)
         else:
-            out, lse = ref.flash_attention_varlen_fwd(qkv, cu_seqlens,
-                                                      max_seqlen, heads, scale)
+            out, lse = ref.flash_attention_varlen_fwd(
+                qkv, cu_seqlens, max_seqlen, heads, scale, causal=causal)
         ctx.save_for_backward(qkv, out, lse, cu_seqlens)
-        ctx.scale, ctx.max_seqlen = scale, max_seqlen
+        ctx.scale, ctx.max_seqlen, ctx.causal = scale, max_seqlen, causal
         return out
 
     @staticmethod
@@ -712,11 +718,12 @@ class FlashAttentionVarlenFn(torch.autograd.Function):
         if qkv.is_cuda and qkv.dtype == torch.bfloat16:
             dqkv = hip_ext().flash_attn_varlen_bwd(
                 qkv, out, dout.contiguous(), lse, cu_seqlens, ctx.max_seqlen,
-                ctx.scale)
+                ctx.scale, ctx.causal)
         else:
             dqkv = ref.flash_attention_varlen_bwd(
-                qkv, out, dout, lse, cu_seqlens, ctx.max_seqlen, ctx.scale)
-        return dqkv, None, None, None, None
+                qkv, out, dout, lse, cu_seqlens, ctx.max_seqlen, ctx.scale,
+                causal=ctx.causal)
+        return dqkv, None, None, None, None, None
 
 
 class FlashAttentionVarlenDropFn(torch.autograd.Function):
@@ -725,13 +732,14 @@ class FlashAttentionVarlenDropFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, cu_seqlens, max_seqlen, heads, scale, p, state,
-                site):
+                site, causal=False):
         qkv = qkv.contiguous()
         state = state.clone()
         out, lse = hip_ext().flash_attn_varlen_drop_fwd(
-            qkv, cu_seqlens, max_seqlen, heads, scale, state, p, site)
+            qkv, cu_seqlens, max_seqlen, heads, scale, state, p, site, causal)
         ctx.save_for_backward(qkv, out, lse, cu_seqlens, state)
         ctx.scale, ctx.max_seqlen, ctx.p, ctx.site = scale, max_seqlen, p, site
+        ctx.causal = causal
         return out
 
     @staticmethod
@@ -739,12 +747,13 @@ class FlashAttentionVarlenDropFn(torch.autograd.Function):
         qkv, out, lse, cu_seqlens, state = ctx.saved_tensors
         dqkv = hip_ext().flash_attn_varlen_drop_bwd(
             qkv, out, dout.contiguous(), lse, cu_seqlens, ctx.max_seqlen,
-            ctx.scale, state, ctx.p, ctx.site)
-        return (dqkv,) + (None,) * 7
+            ctx.scale, state, ctx.p, ctx.site, ctx.causal)
+        return (dqkv,) + (None,) * 8
 
 
 def flash_attention_varlen(qkv, cu_seqlens, max_seqlen, heads, scale,
-                           p: float = 0.0, rng=None, site: int = 0):
+                           p: float = 0.0, rng=None, site: int = 0,
+                           causal: bool = False):
     """Self-attention over a packed, unpadded batch: qkv [T, 3, H, 64] holds
     N sequences back to back, sequence n in rows cu_seqlens[n] ..
     cu_seqlens[n+1] − 1, each attending to itself only → ctx [T, H·64].
@@ -760,13 +769,15 @@ def flash_attention_varlen(qkv, cu_seqlens, max_seqlen, heads, scale,
     CUDA bf16 runs the HIP kernels; anything else the fp32 reference.
     p > 0 (GPU bf16 only): sequence n draws the masks a dense
     [N, max_seqlen] batch draws for batch row n (reference.
-    varlen_attn_dropout_keep)."""
+    varlen_attn_dropout_keep).
+    causal: within each sequence, row i sees the keys j <= i only, positions
+    counted from the sequence start (see flash_attention)."""
     if p == 0:
         return FlashAttentionVarlenFn.apply(qkv, cu_seqlens, max_seqlen, heads,
-                                            scale)
+                                            scale, causal)
     _check_attn_dropout(qkv, p, rng)
     return FlashAttentionVarlenDropFn.apply(qkv, cu_seqlens, max_seqlen, heads,
-                                            scale, p, rng.state, site)
+                                            scale, p, rng.state, site, causal)
 
 
 class BertLayerFn(torch.autograd.Function):

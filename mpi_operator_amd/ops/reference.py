@@ -229,26 +229,32 @@ def dgelu(x):
     return 0.5 * (1 + t) + 0.5 * xf * (1 - t * t) * c * (1 + 3 * 0.044715 * xf * xf)
 
 
-def _flash_scores(qkv, scale: float, mask):
-    """fp32 scaled, masked scores [B,H,S,S] plus q, k, v as [B,H,S,D]."""
+def _flash_scores(qkv, scale: float, mask, causal: bool = False):
+    """fp32 scaled, masked scores [B,H,S,S] plus q, k, v as [B,H,S,D].
+    causal: the keys j > i of row i are excluded (−inf: exactly p = 0)."""
     q, k, v = (qkv[:, :, i].transpose(1, 2).float() for i in range(3))
     s = torch.matmul(q, k.transpose(-1, -2)) * scale
     if mask is not None:
         s = s + mask.float().reshape(qkv.shape[0], 1, 1, qkv.shape[1])
+    if causal:
+        S = qkv.shape[1]
+        future = torch.ones(S, S, dtype=torch.bool, device=qkv.device).triu(1)
+        s = s.masked_fill(future, float("-inf"))
     return s, q, k, v
 
 
 def flash_attention_fwd(qkv, heads: int, scale: float, mask=None, keep=None,
-                        drop_scale: float = 1.0):
+                        drop_scale: float = 1.0, causal: bool = False):
     """Specification of flash_attn_fwd_k. qkv [B,S,3,H,D], mask [B,S]
     additive or None → (ctx [B,S,H·D] in qkv's dtype, lse [B,H,S] fp32).
     Keeps the per-row log-sum-exp, not the probabilities.
     keep (bool [B,H,S,S]) and drop_scale = 1/(1 - p_eff) apply dropout to
     the probabilities: ctx = drop_scale·(P∘keep)·V; lse is that of the
-    undropped softmax."""
+    undropped softmax.
+    causal: row i sees the keys j <= i only (lse is the causal row's)."""
     B, S, _, H, D = qkv.shape
     assert H == heads
-    s, _, _, v = _flash_scores(qkv, scale, mask)
+    s, _, _, v = _flash_scores(qkv, scale, mask, causal)
     lse = torch.logsumexp(s, dim=-1)
     p = torch.exp(s - lse.unsqueeze(-1))
     if keep is not None:
@@ -258,7 +264,8 @@ def flash_attention_fwd(qkv, heads: int, scale: float, mask=None, keep=None,
 
 
 def flash_attention_bwd(qkv, ctx, dctx, lse, scale: float, mask=None,
-                        keep=None, drop_scale: float = 1.0):
+                        keep=None, drop_scale: float = 1.0,
+                        causal: bool = False):
     """Specification of the flash backward kernels: P is recomputed from
     lse and the softmax-gradient row term is delta = rowsum(dctx∘ctx);
     no saved probabilities. Returns dqkv [B,S,3,H,D].
@@ -266,7 +273,7 @@ def flash_attention_bwd(qkv, ctx, dctx, lse, scale: float, mask=None,
     (dO·Vᵀ), dV = drop_scale·(P∘keep)ᵀ·dO, and delta is unchanged, since
     rowsum(dP∘P) = rowsum(dO∘O) still holds for the dropped O."""
     B, S, _, H, D = qkv.shape
-    s, q, k, v = _flash_scores(qkv, scale, mask)
+    s, q, k, v = _flash_scores(qkv, scale, mask, causal)
     p = torch.exp(s - lse.float().unsqueeze(-1))
     do = dctx.reshape(B, S, H, D).transpose(1, 2).float()
     o = ctx.reshape(B, S, H, D).transpose(1, 2).float()
@@ -299,7 +306,8 @@ def _varlen_bounds(cu_seqlens, total: int):
 
 def flash_attention_varlen_fwd(qkv, cu_seqlens, max_seqlen: int, heads: int,
                                scale: float, keep=None,
-                               drop_scale: float = 1.0):
+                               drop_scale: float = 1.0,
+                               causal: bool = False):
     """Specification of the packed (varlen) forward. qkv [T,3,H,D] holds
     N = len(cu_seqlens) − 1 sequences back to back, sequence n in rows
     cu[n]..cu[n+1]−1 → (ctx [T,H·D] in qkv's dtype, lse [H,T] fp32): each
@@ -318,16 +326,18 @@ def flash_attention_varlen_fwd(qkv, cu_seqlens, max_seqlen: int, heads: int,
             raise ValueError(f"sequence {n} has {b - a} > max_seqlen rows")
         kn = keep[n][None] if keep is not None else None
         c, l = flash_attention_fwd(qkv[a:b][None], heads, scale, None, kn,
-                                   drop_scale)
+                                   drop_scale, causal)
         ctx[a:b], lse[:, a:b] = c[0], l[0]
     return ctx, lse
 
 
 def flash_attention_varlen_bwd(qkv, ctx, dctx, lse, cu_seqlens,
                                max_seqlen: int, scale: float, keep=None,
-                               drop_scale: float = 1.0):
+                               drop_scale: float = 1.0,
+                               causal: bool = False):
     """Specification of the packed backward: flash_attention_bwd per
-    sequence slice. Returns dqkv [T,3,H,D], zeros at or past cu[N]."""
+    sequence slice (causal: within each sequence). Returns dqkv [T,3,H,D],
+    zeros at or past cu[N]."""
     T, _, H, D = qkv.shape
     cu = _varlen_bounds(cu_seqlens, T)
     dqkv = torch.zeros_like(qkv)
@@ -337,7 +347,7 @@ def flash_attention_varlen_bwd(qkv, ctx, dctx, lse, cu_seqlens,
         kn = keep[n][None] if keep is not None else None
         dqkv[a:b] = flash_attention_bwd(
             qkv[a:b][None], ctx[a:b][None], dctx[a:b][None],
-            lse[:, a:b][None], scale, None, kn, drop_scale)[0]
+            lse[:, a:b][None], scale, None, kn, drop_scale, causal)[0]
     return dqkv
 
 
