@@ -94,10 +94,11 @@ class BertConfig:
     # kernels on GPU bf16, F.dropout on the eager chain's probs otherwise.
     attn_dropout: float = 0.0
     # Causal (autoregressive) self-attention: token i attends to the tokens
-    # j <= i of its own sequence. GPU bf16 with head_dim 64 runs the causal
-    # flash kernels (Fx.flash_attention / _varlen, causal=True) at any
+    # j <= i of its own sequence. GPU bf16 with head_dim 64 or 128 runs the
+    # causal flash kernels (Fx.flash_attention / _varlen, causal=True) at any
     # sequence length, packed or with no mask or the [b, 1, 1, s] key mask,
-    # provided attention dropout has its rng (p == 0 or rng given); any
+    # provided attention dropout has its rng (p == 0 or rng given; head_dim
+    # 128 has no dropout kernels: p == 0 only); any
     # other mask shape, dtype or device takes the eager chains, which
     # exclude the upper triangle themselves.
     causal: bool = False
@@ -196,6 +197,10 @@ class SelfAttention(nn.Module):
         qkv = self.qkv(x).view(b, s, 3, self.heads, self.head_dim)
         hip = (x.is_cuda and x.dtype == torch.bfloat16 and self.head_dim == 64
                and (p == 0 or rng is not None))
+        # head_dim 128: the flash kernels of flash_attention_d128.hip, which
+        # have no dropout form (p > 0 keeps the eager chains)
+        hip128 = (x.is_cuda and x.dtype == torch.bfloat16
+                  and self.head_dim == 128 and p == 0)
         if cu_seqlens is not None:
             if attn_mask is not None:
                 raise ValueError("a packed batch (cu_seqlens) has no pad "
@@ -204,8 +209,15 @@ class SelfAttention(nn.Module):
                 raise ValueError(f"a packed batch is [1, T, hidden], got "
                                  f"{tuple(x.shape)}")
             return self.out(self._packed(
-                qkv, cu_seqlens, s if max_seqlen is None else max_seqlen, hip,
-                p, rng, site))
+                qkv, cu_seqlens, s if max_seqlen is None else max_seqlen,
+                hip or hip128, p, rng, site))
+        if hip128 and (attn_mask is None or attn_mask.shape == (b, 1, 1, s)):
+            # there is no head_dim 128 form of Fx.attention: any s, causal or
+            # not, whatever MPIAMD_FLASH_ATTN says
+            return self.out(Fx.flash_attention(
+                qkv, self.heads, self.scale,
+                attn_mask.reshape(b, s) if attn_mask is not None else None,
+                causal=self.causal))
         if self.causal and hip and (attn_mask is None
                                     or attn_mask.shape == (b, 1, 1, s)):
             # the causal kernels exist in flash_attention.hip only: any s,

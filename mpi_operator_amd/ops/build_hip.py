@@ -19,7 +19,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "hipcc")
 
 KERNEL_SRCS = ["elementwise.hip", "batchnorm.hip", "pooling.hip",
-               "softmax_xent.hip", "masked_xent.hip", "attention.hip", "flash_attention.hip", "gemm.hip", "conv.hip", "layernorm.hip",
+               "softmax_xent.hip", "masked_xent.hip", "attention.hip", "flash_attention.hip", "flash_attention_d128.hip", "gemm.hip", "conv.hip", "layernorm.hip",
                "optimizer.hip", "dropout.hip", "embedding.hip",
                "mlm_select.hip"]
 BINDING_SRC = "bindings.cpp"

@@ -1462,12 +1462,14 @@ static Tensor attn_bwd(const Tensor &qkv, const Tensor &dctx,
 }
 
 // ------------------- tiled attention (any S, key mask) -------------------
-// qkv: [B, S, 3, H, 64]; returns (ctx [B, S, H*64], lse [B, H, S] fp32).
+// qkv: [B, S, 3, H, D], D = 64 (flash_attention.hip) or 128
+// (flash_attention_d128.hip); returns (ctx [B, S, H*D], lse [B, H, S] fp32).
 // No probs: the backward recomputes P from lse.
 static void flash_check_qkv(const Tensor &qkv, int64_t heads) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 && qkv.size(4) == 64,
-              "qkv must be [B,S,3,H,64]");
+  TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 &&
+                  (qkv.size(4) == 64 || qkv.size(4) == 128),
+              "qkv must be [B,S,3,H,D] with D 64 or 128, got ", qkv.sizes());
   TORCH_CHECK(qkv.is_contiguous());
   TORCH_CHECK(qkv.size(3) == heads);
   TORCH_CHECK(qkv.size(0) >= 1 && qkv.size(1) >= 1);
@@ -1489,11 +1491,11 @@ static std::vector<Tensor> flash_attn_fwd(const Tensor &qkv, int64_t heads,
                                           bool causal) {
   flash_check_qkv(qkv, heads);
   const HIPDeviceGuard guard(qkv.device());
-  int B = qkv.size(0), S = qkv.size(1), H = qkv.size(3);
+  int B = qkv.size(0), S = qkv.size(1), H = qkv.size(3), D = qkv.size(4);
   Tensor maskc = flash_mask(mask, B, S);
-  Tensor ctx = at::empty({B, S, (long)H * 64}, qkv.options());
+  Tensor ctx = at::empty({B, S, (long)H * D}, qkv.options());
   Tensor lse = at::empty({B, (long)H, S}, qkv.options().dtype(at::kFloat));
-  CHK(flash_attn_fwd_launch(
+  CHK((D == 128 ? flash128_fwd_launch : flash_attn_fwd_launch)(
       qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr<float>(),
       maskc.defined() ? maskc.data_ptr<float>() : nullptr, B, S, H,
       (float)scale, causal, cur_stream()));
@@ -1506,12 +1508,12 @@ static Tensor flash_attn_bwd(const Tensor &qkv, const Tensor &ctx,
                              const c10::optional<Tensor> &mask, bool causal) {
   flash_check_qkv(qkv, qkv.dim() == 5 ? qkv.size(3) : 0);
   const HIPDeviceGuard guard(qkv.device());
-  int B = qkv.size(0), S = qkv.size(1), H = qkv.size(3);
+  int B = qkv.size(0), S = qkv.size(1), H = qkv.size(3), D = qkv.size(4);
   TORCH_CHECK(ctx.is_cuda() && ctx.scalar_type() == at::kBFloat16 &&
-              ctx.is_contiguous() && ctx.numel() == (long)B * S * H * 64,
-              "ctx must be [B,S,H*64] bf16");
+              ctx.is_contiguous() && ctx.numel() == (long)B * S * H * D,
+              "ctx must be [B,S,H*D] bf16");
   TORCH_CHECK(dctx.is_cuda() && dctx.scalar_type() == at::kBFloat16 &&
-              dctx.numel() == ctx.numel(), "dctx must be [B,S,H*64] bf16");
+              dctx.numel() == ctx.numel(), "dctx must be [B,S,H*D] bf16");
   TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat &&
               lse.is_contiguous() && lse.numel() == (long)B * H * S,
               "lse must be [B,H,S] fp32");
@@ -1519,7 +1521,7 @@ static Tensor flash_attn_bwd(const Tensor &qkv, const Tensor &ctx,
   Tensor dc = dctx.contiguous();
   Tensor delta = at::empty_like(lse);
   Tensor dqkv = at::empty_like(qkv);
-  CHK(flash_attn_bwd_launch(
+  CHK((D == 128 ? flash128_bwd_launch : flash_attn_bwd_launch)(
       qkv.data_ptr(), ctx.data_ptr(), dc.data_ptr(), lse.data_ptr<float>(),
       delta.data_ptr<float>(),
       maskc.defined() ? maskc.data_ptr<float>() : nullptr, dqkv.data_ptr(), B,
@@ -1539,7 +1541,8 @@ static AttnDropShape check_attn_drop_qkv(const Tensor &qkv, int64_t heads,
               " must be a bf16 GPU tensor");
   TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3 && qkv.size(4) == 64 &&
                   qkv.size(0) >= 1 && qkv.size(1) >= 1 && qkv.size(3) >= 1,
-              name, " must be [B,S,3,H,64], got ", qkv.sizes());
+              name, " must be [B,S,3,H,64] (attention dropout at head dim "
+              "128 is not built), got ", qkv.sizes());
   TORCH_CHECK(qkv.is_contiguous(), name, " must be contiguous");
   TORCH_CHECK(heads < 0 || qkv.size(3) == heads, name, " has ", qkv.size(3),
               " heads, expected ", heads);
@@ -1665,20 +1668,26 @@ static Tensor flash_attn_drop_bwd_b(const Tensor &qkv, const Tensor &ctx,
 }
 
 // ------------------ packed (varlen) tiled attention ------------------
-// qkv [T,3,H,64]: N sequence slots back to back, cu_seqlens device int32
+// qkv [T,3,H,D] (D = 64, or 128 without dropout): N sequence slots back to back, cu_seqlens device int32
 // [N+1] (cu[0] = 0, non-decreasing, cu[N] <= T, no length above max_seqlen:
 // preconditions, never read on the host — nothing here syncs). Returns
-// (ctx [T,H*64], lse [H,T] fp32); rows at or past cu[N] are zeros.
+// (ctx [T,H*D], lse [H,T] fp32); rows at or past cu[N] are zeros.
 struct VarlenShape {
-  int N, T, H, max_seqlen;
+  int N, T, H, max_seqlen, D;
 };
+// d128: the dropout-free bindings pass true, the *_drop_* ones false
 static VarlenShape check_varlen_qkv(const Tensor &qkv, int64_t heads,
-                                    const Tensor &cu, int64_t max_seqlen) {
+                                    const Tensor &cu, int64_t max_seqlen,
+                                    bool d128 = false) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16,
               "qkv must be a bf16 GPU tensor");
-  TORCH_CHECK(qkv.dim() == 4 && qkv.size(1) == 3 && qkv.size(3) == 64 &&
+  TORCH_CHECK(qkv.dim() == 4 && qkv.size(1) == 3 &&
+                  (qkv.size(3) == 64 || (d128 && qkv.size(3) == 128)) &&
                   qkv.size(0) >= 1 && qkv.size(2) >= 1,
-              "qkv must be [T,3,H,64], got ", qkv.sizes());
+              d128 ? "qkv must be [T,3,H,D] with D 64 or 128, got "
+                   : "qkv must be [T,3,H,64] (attention dropout at head dim "
+                     "128 is not built), got ",
+              qkv.sizes());
   TORCH_CHECK(qkv.is_contiguous(), "qkv must be contiguous");
   TORCH_CHECK(heads < 0 || qkv.size(2) == heads, "qkv has ", qkv.size(2),
               " heads, expected ", heads);
@@ -1692,15 +1701,16 @@ static VarlenShape check_varlen_qkv(const Tensor &qkv, int64_t heads,
               "max_seqlen must be a positive int32, got ", max_seqlen);
   long N = cu.numel() - 1;
   TORCH_CHECK(N * qkv.size(2) < (1L << 31), "N*H must fit an int32");
-  return {(int)N, (int)qkv.size(0), (int)qkv.size(2), (int)max_seqlen};
+  return {(int)N, (int)qkv.size(0), (int)qkv.size(2), (int)max_seqlen,
+          (int)qkv.size(3)};
 }
 
 static void check_varlen_ctx(const Tensor &t, const Tensor &qkv,
                              const VarlenShape &d, const char *name) {
   TORCH_CHECK(t.is_cuda() && t.device() == qkv.device() &&
                   t.scalar_type() == at::kBFloat16 && t.is_contiguous() &&
-                  t.numel() == (long)d.T * d.H * 64,
-              name, " must be a contiguous bf16 [T,H*64] tensor on qkv's GPU");
+                  t.numel() == (long)d.T * d.H * d.D,
+              name, " must be a contiguous bf16 [T,H*D] tensor on qkv's GPU");
 }
 
 static void check_varlen_lse(const Tensor &lse, const Tensor &qkv,
@@ -1723,11 +1733,12 @@ static std::vector<Tensor> flash_attn_varlen_fwd(const Tensor &qkv,
                                                  int64_t max_seqlen,
                                                  int64_t heads, double scale,
                                                  bool causal) {
-  const VarlenShape d = check_varlen_qkv(qkv, heads, cu_seqlens, max_seqlen);
+  const VarlenShape d =
+      check_varlen_qkv(qkv, heads, cu_seqlens, max_seqlen, true);
   const HIPDeviceGuard guard(qkv.device());
-  Tensor ctx = at::empty({d.T, (long)d.H * 64}, qkv.options());
+  Tensor ctx = at::empty({d.T, (long)d.H * d.D}, qkv.options());
   Tensor lse = at::empty({(long)d.H, d.T}, qkv.options().dtype(at::kFloat));
-  CHK(flash_attn_varlen_fwd_launch(
+  CHK((d.D == 128 ? flash128_varlen_fwd_launch : flash_attn_varlen_fwd_launch)(
       qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr<float>(),
       cu_seqlens.data_ptr<int>(), d.N, d.T, d.max_seqlen, d.H, (float)scale,
       causal, cur_stream()));
@@ -1739,14 +1750,15 @@ static Tensor flash_attn_varlen_bwd(const Tensor &qkv, const Tensor &ctx,
                                     const Tensor &cu_seqlens,
                                     int64_t max_seqlen, double scale,
                                     bool causal) {
-  const VarlenShape d = check_varlen_qkv(qkv, -1, cu_seqlens, max_seqlen);
+  const VarlenShape d =
+      check_varlen_qkv(qkv, -1, cu_seqlens, max_seqlen, true);
   check_varlen_ctx(ctx, qkv, d, "ctx");
   check_varlen_ctx(dctx, qkv, d, "dctx");
   check_varlen_lse(lse, qkv, d);
   const HIPDeviceGuard guard(qkv.device());
   Tensor delta = at::empty_like(lse);
   Tensor dqkv = at::empty_like(qkv);
-  CHK(flash_attn_varlen_bwd_launch(
+  CHK((d.D == 128 ? flash128_varlen_bwd_launch : flash_attn_varlen_bwd_launch)(
       qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr<float>(),
       delta.data_ptr<float>(), cu_seqlens.data_ptr<int>(), dqkv.data_ptr(),
       d.N, d.T, d.max_seqlen, d.H, (float)scale, causal, cur_stream()));

@@ -241,6 +241,28 @@ hipError_t flash_attn_varlen_drop_bwd_launch(
     uint32_t thr, float rs, void *dqkv, int N, int T, int max_seqlen, int H,
     float scale, int causal, hipStream_t strm);
 
+// ---- flash_attention_d128.hip ----
+// the dropout-free entry points above at head_dim 128: the same arguments
+// and layouts with 128 in place of 64
+hipError_t flash128_fwd_launch(const void *qkv, void *ctx, float *lse,
+                               const float *mask, int B, int S, int H,
+                               float scale, int causal, hipStream_t strm);
+hipError_t flash128_bwd_launch(const void *qkv, const void *ctx,
+                               const void *dctx, const float *lse,
+                               float *delta, const float *mask, void *dqkv,
+                               int B, int S, int H, float scale, int causal,
+                               hipStream_t strm);
+hipError_t flash128_varlen_fwd_launch(const void *qkv, void *ctx, float *lse,
+                                      const int *cu_seqlens, int N, int T,
+                                      int max_seqlen, int H, float scale,
+                                      int causal, hipStream_t strm);
+hipError_t flash128_varlen_bwd_launch(const void *qkv, const void *ctx,
+                                      const void *dctx, const float *lse,
+                                      float *delta, const int *cu_seqlens,
+                                      void *dqkv, int N, int T, int max_seqlen,
+                                      int H, float scale, int causal,
+                                      hipStream_t strm);
+
 // ---- gemm.hip ----
 hipError_t gemm_nt(const void *a, const void *b, void *c, int M, int N, int K,
                    long lda, long ldb, long ldc, int c_f32, hipStream_t s);

@@ -598,6 +598,9 @@ def _check_attn_dropout(qkv, p, rng):
         raise ValueError("attention dropout (p > 0) runs on GPU bf16 only")
     if rng is None:
         raise ValueError("attention dropout (p > 0) needs a DropoutRng")
+    if qkv.shape[-1] != 64:
+        raise ValueError(f"attention dropout (p > 0) is built for head dim "
+                         f"64 only, got {qkv.shape[-1]}")
 
 
 def attention(qkv, heads, scale, mask=None, p: float = 0.0, rng=None,
@@ -612,11 +615,12 @@ def attention(qkv, heads, scale, mask=None, p: float = 0.0, rng=None,
 
 
 class FlashAttentionFn(torch.autograd.Function):
-    """Tiled online-softmax MHA (ops/csrc/flash_attention.hip): any sequence
-    length, optional additive key mask [B, S]. Saves qkv, ctx, the per-row
-    log-sum-exp [B, H, S] and the mask — no [B, H, S, S] probs; the backward
-    recomputes P from lse (deterministic, no atomics).
-    qkv: [B, S, 3, H, 64] → ctx [B, S, H·64]."""
+    """Tiled online-softmax MHA (ops/csrc/flash_attention.hip, head dim 128:
+    flash_attention_d128.hip): any sequence length, optional additive key
+    mask [B, S]. Saves qkv, ctx, the per-row log-sum-exp [B, H, S] and the
+    mask — no [B, H, S, S] probs; the backward recomputes P from lse
+    (deterministic, no atomics).
+    qkv: [B, S, 3, H, D] → ctx [B, S, H·D], D in {64, 128}."""
 
     @staticmethod
     def forward(ctx, qkv, heads, scale, mask, causal=False):
@@ -671,15 +675,16 @@ class FlashAttentionDropFn(torch.autograd.Function):
 
 def flash_attention(qkv, heads, scale, mask=None, p: float = 0.0, rng=None,
                     site: int = 0, causal: bool = False):
-    """softmax(Q·Kᵀ·scale + mask)·V for qkv [B, S, 3, H, 64] → [B, S, H·64].
+    """softmax(Q·Kᵀ·scale + mask)·V for qkv [B, S, 3, H, D] → [B, S, H·D],
+    D in {64, 128} on the GPU.
 
     mask: optional additive key mask [B, S] (0 = keep, a large negative
     such as finfo(float32).min = drop), shared by all heads and query rows.
     CUDA bf16 runs the HIP kernels; anything else the fp32 reference.
     A batch row with NO valid key is outside the contract: its output and
     gradients are only guaranteed to be finite.
-    p > 0 (GPU bf16 only) drops out the softmax output with masks from
-    `rng` at call site `site`; p == 0 is the dropout-free path itself.
+    p > 0 (GPU bf16, D = 64 only) drops out the softmax output with masks
+    from `rng` at call site `site`; p == 0 is the dropout-free path itself.
     causal: query row i sees the keys j <= i only (autoregressive); the HIP
     kernels then skip the key tiles in the future instead of masking them.
     It combines with `mask` (a key is dropped if it is masked or in the
@@ -693,11 +698,12 @@ def flash_attention(qkv, heads, scale, mask=None, p: float = 0.0, rng=None,
 
 class FlashAttentionVarlenFn(torch.autograd.Function):
     """FlashAttentionFn over a packed batch (the VARLEN kernels of
-    ops/csrc/flash_attention.hip): qkv [T, 3, H, 64] holds the sequences back
-    to back, cu_seqlens (int32 [N + 1], on qkv's device) their bounds.
+    ops/csrc/flash_attention.hip and flash_attention_d128.hip): qkv
+    [T, 3, H, D], D in {64, 128}, holds the sequences back to back,
+    cu_seqlens (int32 [N + 1], on qkv's device) their bounds.
     Saves qkv, ctx, lse [H, T] and cu_seqlens; cu_seqlens is read on the
     device only, so nothing syncs and a captured call replays on new lengths.
-    → ctx [T, H·64]."""
+    → ctx [T, H·D]."""
 
     @staticmethod
     def forward(ctx, qkv, cu_seqlens, max_seqlen, heads, scale, causal=False):
@@ -754,9 +760,10 @@ class FlashAttentionVarlenDropFn(torch.autograd.Function):
 def flash_attention_varlen(qkv, cu_seqlens, max_seqlen, heads, scale,
                            p: float = 0.0, rng=None, site: int = 0,
                            causal: bool = False):
-    """Self-attention over a packed, unpadded batch: qkv [T, 3, H, 64] holds
-    N sequences back to back, sequence n in rows cu_seqlens[n] ..
-    cu_seqlens[n+1] − 1, each attending to itself only → ctx [T, H·64].
+    """Self-attention over a packed, unpadded batch: qkv [T, 3, H, D], D in
+    {64, 128} on the GPU, holds N sequences back to back, sequence n in rows
+    cu_seqlens[n] .. cu_seqlens[n+1] − 1, each attending to itself only →
+    ctx [T, H·D].
 
     cu_seqlens: int32 [N + 1] on qkv's device with cu[0] = 0, non-decreasing
     (an empty slot repeats a value) and cu[N] <= T; max_seqlen: a host int no
@@ -767,7 +774,7 @@ def flash_attention_varlen(qkv, cu_seqlens, max_seqlen, heads, scale,
     Rows at or past cu[N] (the unused tail of a token budget) come back as
     zeros, and so do their gradients.
     CUDA bf16 runs the HIP kernels; anything else the fp32 reference.
-    p > 0 (GPU bf16 only): sequence n draws the masks a dense
+    p > 0 (GPU bf16, D = 64 only): sequence n draws the masks a dense
     [N, max_seqlen] batch draws for batch row n (reference.
     varlen_attn_dropout_keep).
     causal: within each sequence, row i sees the keys j <= i only, positions
