@@ -164,7 +164,9 @@ __global__ __launch_bounds__(256) void attn_fwd_k(
 #pragma unroll
     for (int off = 16; off > 0; off >>= 1)
       s += __shfl_xor(s, off, 64);
-    srow[r] = 1.f / s;
+    // a row with no valid key at S == S_MAX (no padded column, whose e = 1
+    // would otherwise hold the sum up) has every e = 0: P = 0, not 0·inf
+    srow[r] = s > 0.f ? 1.f / s : 0.f;
   }
 
   // keep bits of this lane's 16 registers per column fragment (two Philox
