@@ -39,6 +39,13 @@ def _try_load():
         pair = os.environ.get("MPIAMD_PAIR_BWD", "1")
         if pair != "1":
             _ext.set_pair_bwd(pair == "2", pair == "2")
+        # MPIAMD_PAIR_REDUCE (default "2"): after such a pair, the dx reduce
+        # (with its BN-backward stats) and the dw reduce share one launch, dx
+        # blocks first; "1" puts the dw blocks first, "0" keeps the two
+        # launches (A/B levers)
+        rpair = os.environ.get("MPIAMD_PAIR_REDUCE", "2")
+        if rpair != "2":
+            _ext.set_pair_reduce(rpair == "1", False)
         # MPIAMD_BN_PIPELINED (default "1"): software-pipelined BN statistics
         # producers; MPIAMD_BN_FINALIZE_COALESCED (default "1"): line-coalesced
         # BN finalize. "0" keeps the kernels they replace (A/B levers)

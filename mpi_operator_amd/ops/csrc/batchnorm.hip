@@ -8,6 +8,7 @@
 #include "common.h"
 #include "knobs.h"
 #include "launchers.h"
+#include "reduce_pair.h"
 #include <atomic>
 
 // Per-thread fixed channel-group ownership: thread t owns channel block
@@ -115,98 +116,10 @@ __global__ void bn_partials_k(const ushort8 *__restrict__ x,
   }
 }
 
-// Accumulation steps and the block tail of bn_partials_k above, restated for
-// the split-K reduce+stats kernels below: same row assignment, same order,
-// same roundings, so a statistic computed there is bit-identical to the one
-// bn_partials_k computes from the same (rounded) tensor
-// (tests/test_conv_bn_fused_gpu.py asserts equality). bn_partials_k keeps its
-// own text so its code, and with it every unfused result, stays as it was.
-DEV_INLINE void bn_acc_fwd(float *a0, float *a1, const float *fx,
-                           const float *fx2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    a0[j] += fx[j] + fx2[j];
-    a1[j] += fx[j] * fx[j] + fx2[j] * fx2[j];
-  }
-}
-
-// fdy/fdy2 are gated in place by the ReLU mask (bitmask if given, else y>0)
-DEV_INLINE void bn_acc_bwd(float *a0, float *a1, const float *fx,
-                           const float *fx2, float *fdy, float *fdy2,
-                           const ushort8 *__restrict__ y,
-                           const uint8_t *__restrict__ mask, long off,
-                           long off2, bool has2, int relu, const float *mn,
-                           const float *is) {
-  if (relu) {
-    if (mask) {
-      int m1 = mask[off], m2 = has2 ? mask[off2] : 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (!(m1 & (1 << j))) fdy[j] = 0.f;
-        if (!(m2 & (1 << j))) fdy2[j] = 0.f;
-      }
-    } else {
-      ushort8 vy = y[off];
-      ushort8 vy2 = has2 ? y[off2] : ushort8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (!(bf2f(vy[j]) > 0.f)) fdy[j] = 0.f;
-        if (!(bf2f(vy2[j]) > 0.f)) fdy2[j] = 0.f;
-      }
-    }
-  }
-  // roundings spelled out as bn_partials_k<1> compiles them (one fma per
-  // channel: dy·x̂ + the second row's rounded product), so the contraction
-  // does not depend on the surrounding code
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    a0[j] += fdy[j] + fdy2[j];
-    float xh = __fmul_rn(__fsub_rn(fx[j], mn[j]), is[j]);
-    float xh2 = __fmul_rn(__fsub_rn(fx2[j], mn[j]), is[j]);
-    a1[j] = __fadd_rn(a1[j], __fmaf_rn(fdy[j], xh, __fmul_rn(fdy2[j], xh2)));
-  }
-}
-
-// block reduce across row lanes via LDS, row lane 0 stores the slab entry
-DEV_INLINE void bn_block_store(float *a0, float *a1,
-                               float *__restrict__ partial, int C8, int cb,
-                               int row_lane, int rows_per_block) {
-  int C = C8 * 8;
-  __shared__ float lds[2][256 * 8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    lds[0][threadIdx.x * 8 + j] = a0[j];
-    lds[1][threadIdx.x * 8 + j] = a1[j];
-  }
-  __syncthreads();
-  if (row_lane == 0) {
-    for (int rl = 1; rl < rows_per_block; ++rl) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        a0[j] += lds[0][(rl * C8 + cb) * 8 + j];
-        a1[j] += lds[1][(rl * C8 + cb) * 8 + j];
-      }
-    }
-    float *p0 = partial + (long)blockIdx.x * 2 * C + cb * 8;
-    float *p1 = p0 + C;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      p0[j] = a0[j];
-      p1[j] = a1[j];
-    }
-  }
-}
-
-// Split-K reduce fused with the BN partials pass, in bn_partials_k's exact
-// geometry (a thread owns one 8-channel group, the block strides over rows,
-// grid from bn_geom). Per row: sum the `splits` fp32 slabs in
-// splitk_reduce_k's order, round ONCE to bf16, write the tensor, and
-// accumulate the statistics of the ROUNDED values — so the tensor is
-// bit-identical to splitk_reduce's and the slab to bn_partials_k's, while
-// the activation is never re-read.
-//   WHAT 0 (forward):  out = conv output y;  slab = Σy, Σy²
-//   WHAT 1 (backward): out = dgrad output dy; slab = Σ(dy·m), Σ(dy·m·x̂)
-//     with x = the consumer BN's saved pre-BN activation.
+// bn_acc_fwd, bn_acc_bwd and bn_block_store (the accumulation steps and the
+// block tail of bn_partials_k above, restated) and the body of the split-K
+// reduce + BN partials kernel live in reduce_pair.h, which conv.hip shares
+// for the pair reduce; this kernel is that body on its own grid.
 template <int WHAT, int SPLITS>
 __global__ void bn_reduce_stats_k(const float4v *__restrict__ slabs,
                                   int splits_rt, long len4,
@@ -218,66 +131,9 @@ __global__ void bn_reduce_stats_k(const float4v *__restrict__ slabs,
                                   const float *__restrict__ invstd,
                                   float *__restrict__ partial, // [grid][2][C]
                                   long M, int C8, int relu) {
-  int cb = threadIdx.x % C8;
-  int row_lane = threadIdx.x / C8;
-  int rows_per_block = blockDim.x / C8;
-  float a0[8] = {0}, a1[8] = {0};
-  float mn[8], is[8];
-  if (WHAT == 1 && row_lane < rows_per_block) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      mn[j] = mean[cb * 8 + j];
-      is[j] = invstd[cb * 8 + j];
-    }
-  }
-  if (row_lane < rows_per_block) {
-    long stride = (long)gridDim.x * rows_per_block;
-    for (long row = (long)blockIdx.x * rows_per_block + row_lane; row < M;
-         row += 2 * stride) {
-      long r2 = row + stride;
-      bool has2 = r2 < M;
-      long off = row * C8 + cb, off2 = r2 * C8 + cb;
-      // 8 channels = two float4 slab lanes per row; both rows' chains issue
-      // before either is consumed
-      float4v s0 = splitk_sum4<SPLITS>(slabs, splits_rt, len4, off * 2);
-      float4v s1 = splitk_sum4<SPLITS>(slabs, splits_rt, len4, off * 2 + 1);
-      float4v t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
-      if (has2) {
-        t0 = splitk_sum4<SPLITS>(slabs, splits_rt, len4, off2 * 2);
-        t1 = splitk_sum4<SPLITS>(slabs, splits_rt, len4, off2 * 2 + 1);
-      }
-      ushort8 vo, vo2 = ushort8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        vo[j] = f2bf(s0[j]);
-        vo[4 + j] = f2bf(s1[j]);
-      }
-      out[off] = vo;
-      if (has2) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          vo2[j] = f2bf(t0[j]);
-          vo2[4 + j] = f2bf(t1[j]);
-        }
-        out[off2] = vo2;
-      }
-      float fo[8], fo2[8];
-      bf8_to_f8(vo, fo);
-      bf8_to_f8(vo2, fo2);
-      if (WHAT == 0) {
-        bn_acc_fwd(a0, a1, fo, fo2);
-      } else {
-        float fx[8], fx2[8];
-        ushort8 vx = x[off];
-        ushort8 vx2 = has2 ? x[off2] : ushort8{0, 0, 0, 0, 0, 0, 0, 0};
-        bf8_to_f8(vx, fx);
-        bf8_to_f8(vx2, fx2);
-        bn_acc_bwd(a0, a1, fx, fx2, fo, fo2, y, mask, off, off2, has2, relu,
-                   mn, is);
-      }
-    }
-  }
-  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block);
+  bn_reduce_stats_body<WHAT, SPLITS>(slabs, splits_rt, len4, out, x, y, mask,
+                                     mean, invstd, partial, M, C8, relu,
+                                     blockIdx.x, gridDim.x);
 }
 
 // Residual-join gradient fused with the BN partials pass of the BN layer(s)
@@ -381,12 +237,14 @@ bn_join_stats_k(const ushort8 *__restrict__ a,
       }
     }
   }
-  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block);
+  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block,
+                 blockIdx.x);
   if (NSTAT == 2) {
     // bn_block_store's LDS array is one static allocation: row lane 0 must
     // finish reading the first reduction before anyone overwrites it
     __syncthreads();
-    bn_block_store(d0, d1, partial_d, C8, cb, row_lane, rows_per_block);
+    bn_block_store(d0, d1, partial_d, C8, cb, row_lane, rows_per_block,
+                   blockIdx.x);
   }
 }
 
@@ -793,7 +651,8 @@ bn_partials_bwd_pipe_k(const ushort8 *__restrict__ x,
       }
     }
   }
-  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block);
+  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block,
+                 blockIdx.x);
 }
 
 struct BnJoinStage {
@@ -897,10 +756,12 @@ bn_join_stats_pipe_k(const ushort8 *__restrict__ a,
       }
     }
   }
-  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block);
+  bn_block_store(a0, a1, partial, C8, cb, row_lane, rows_per_block,
+                 blockIdx.x);
   if (NSTAT == 2) {
     __syncthreads(); // one static LDS array, as in bn_join_stats_k
-    bn_block_store(d0, d1, partial_d, C8, cb, row_lane, rows_per_block);
+    bn_block_store(d0, d1, partial_d, C8, cb, row_lane, rows_per_block,
+                   blockIdx.x);
   }
 }
 

@@ -2320,6 +2320,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_pair_bwd", [](bool on, bool dgrad_first) {
     return conv_set_pair_bwd(on ? (dgrad_first ? 2 : 1) : 0);
   }, py::arg("on"), py::arg("dgrad_first") = false);
+  // the dx reduce (+ BN-backward stats) and the dw reduce after such a pair
+  // as one grid or as the two launches they were; stats_first puts the dx
+  // blocks at the front of the grid (the process default, which
+  // set_pair_reduce(True, True) names). Returns the mode it replaces, as
+  // MPIAMD_PAIR_REDUCE numbers them: 0 two launches, 1 one grid dw first,
+  // 2 one grid dx first; set_pair_reduce(prev != 0, prev == 2) restores it.
+  m.def("set_pair_reduce", [](bool on, bool stats_first) {
+    return conv_set_pair_reduce(on ? (stats_first ? 2 : 1) : 0);
+  }, py::arg("on"), py::arg("stats_first") = false);
+  // how many pair-reduce launches this process has issued
+  m.def("pair_reduce_count", []() { return (int64_t)conv_pair_reduce_count(); });
   m.def("pipe8_gemm_pair", &pipe8_gemm_pair_b, py::arg("a1"), py::arg("b1"),
         py::arg("c1"), py::arg("n1"), py::arg("a2"), py::arg("b2"),
         py::arg("c2"), py::arg("n2"), py::arg("paired"),

@@ -14,6 +14,7 @@
 #include "launchers.h"
 #include "mfma_tile.h"
 #include "mix_gemm.h"
+#include "reduce_pair.h"
 
 // Custom NT stager for conv fwd: the 4 staged rows (output pixels) are
 // FIXED for the whole kernel, so their (n, ho, wo) decomposition is hoisted
@@ -577,26 +578,13 @@ extern "C" hipError_t conv_dgrad_bn(const void *dy, const void *w, void *dx,
 }
 
 
-// float4 lanes; SPLITS is a template parameter for the common counts so
-// the accumulation loop FULLY UNROLLS — the runtime-splits version issued
-// its slab loads as a 2-chain serial loop and sat 73% wave-parked (PMC),
-// 4.7x off bandwidth at the BERT dw shapes.
+// the split-K reduce on its own grid (body: reduce_pair.h)
 template <bool OUT_BF16, int SPLITS = 0>
 __global__ void splitk_reduce_k(const float4v *__restrict__ partial,
                                 int splits_rt, long len4,
                                 void *__restrict__ out) {
-  for (long i = blockIdx.x * blockDim.x + threadIdx.x; i < len4;
-       i += (long)gridDim.x * blockDim.x) {
-    // summation order lives in common.h (shared with the BN-stats reduces)
-    float4v a = splitk_sum4<SPLITS>(partial, splits_rt, len4, i);
-    if (OUT_BF16) {
-      uint16_t *o = (uint16_t *)out + i * 4;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = f2bf(a[j]);
-    } else {
-      ((float4v *)out)[i] = a;
-    }
-  }
+  splitk_reduce_body<OUT_BF16, SPLITS>(partial, splits_rt, len4, out,
+                                       blockIdx.x, gridDim.x);
 }
 
 // Split-K reduce + bias epilogue for FORWARD activations (bf16 out): the
@@ -678,13 +666,17 @@ extern "C" hipError_t slab_colreduce(const float *partial, float *out,
   return hipSuccess;
 }
 
+// grid of splitk_reduce_k, and of its blocks within a pair reduce
+static int splitk_reduce_blocks(long len4) {
+  long blocks = (len4 + 255) / 256;
+  return (int)(blocks > 2048 ? 2048 : blocks);
+}
+
 extern "C" hipError_t splitk_reduce(const float *partial, int splits, long len,
                                     void *out, int out_bf16, hipStream_t s) {
   long len4 = len / 4; // len = Kout*RSC, both %8 ⇒ %4
-  long blocks = (len4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
   const float4v *p4 = (const float4v *)partial;
-  int nb = (int)blocks;
+  int nb = splitk_reduce_blocks(len4);
 #define SKR_DISPATCH(BF)                                                        do {                                                                            switch (splits) {                                                             case 2: splitk_reduce_k<BF, 2><<<nb, 256, 0, s>>>(p4, splits, len4, out); break;     case 3: splitk_reduce_k<BF, 3><<<nb, 256, 0, s>>>(p4, splits, len4, out); break;     case 4: splitk_reduce_k<BF, 4><<<nb, 256, 0, s>>>(p4, splits, len4, out); break;     case 5: splitk_reduce_k<BF, 5><<<nb, 256, 0, s>>>(p4, splits, len4, out); break;     case 6: splitk_reduce_k<BF, 6><<<nb, 256, 0, s>>>(p4, splits, len4, out); break;     case 8: splitk_reduce_k<BF, 8><<<nb, 256, 0, s>>>(p4, splits, len4, out); break;     case 16: splitk_reduce_k<BF, 16><<<nb, 256, 0, s>>>(p4, splits, len4, out); break;     default: splitk_reduce_k<BF, 0><<<nb, 256, 0, s>>>(p4, splits, len4, out); break;     }                                                                           } while (0)
   if (out_bf16)
     SKR_DISPATCH(true);
@@ -829,6 +821,78 @@ extern "C" hipError_t pipe8_gemm_pair(const void *a1, const void *b1, float *c1,
                              splits2 > 1, strm, splits2);
 }
 
+// ---- paired reduces: the dx and dw split-K reduces after a backward pair ----
+// Process-wide switch, set through the extension's set_pair_reduce(); the
+// Python side owns MPIAMD_PAIR_REDUCE and calls this once at load.
+// 0: two launches; 1: one grid, dw blocks first; 2: dx (stats) blocks first,
+// the default: they run longer, and starting them first measured faster.
+static std::atomic<int> g_pair_reduce{2};
+// pair-reduce launches issued by this process (the tests' proof of the route)
+static std::atomic<long> g_pair_reduce_count{0};
+
+extern "C" int conv_set_pair_reduce(int mode) {
+  return g_pair_reduce.exchange(mode < 0 || mode > 2 ? 0 : mode,
+                                std::memory_order_relaxed);
+}
+
+extern "C" long conv_pair_reduce_count() {
+  return g_pair_reduce_count.load(std::memory_order_relaxed);
+}
+
+// The (dx splits, dw form) combinations reduce_pair_k is built for: those of
+// the stride-1 convs of ResNet50 and ResNet101 at batch 64 whose dgrad
+// splits. The dw form is splitk_reduce's dispatch of the dw split count: the
+// count itself where it has a template instance, else 0, the runtime loop
+// (24 at the 14x14 conv3, 1 at small shapes).
+#define REDUCE_PAIR_TABLE(X) X(2, 8) X(2, 0) X(4, 6) X(5, 3)
+
+static int splitk_reduce_form(int splits) {
+  switch (splits) {
+  case 2: case 3: case 4: case 5: case 6: case 8: case 16: return splits;
+  default: return 0;
+  }
+}
+
+// Both reduces of a conv backward pair as one grid of nb_dw + nb_dx blocks,
+// each side with the grid its own launch has (splitk_reduce's block count,
+// bn_stats_grid). stats: the dx side also writes the BN-backward slab.
+// Returns false, having launched nothing, when the switch is off or the
+// combination is not in the table: the caller then issues the two launches.
+static bool conv_reduce_pair(bool stats, const float *dpartial, int dsplits,
+                             void *dx, long M, int C, const void *bx,
+                             const void *by, const uint8_t *mask,
+                             const float *mean, const float *invstd, int relu,
+                             float *bn_slab, const float *wpartial,
+                             int wsplits, long wlen, void *dw,
+                             hipStream_t strm) {
+  const int mode = g_pair_reduce.load(std::memory_order_relaxed);
+  const int C8 = C / 8;
+  if (!mode || C % 8 != 0 || C8 < 1 || C8 > 256 || M < 1) return false;
+  const long dlen4 = M * C / 4, wlen4 = wlen / 4;
+  const int nb_dx = stats ? bn_stats_grid(M, C) : splitk_reduce_blocks(dlen4);
+  const int nb_dw = splitk_reduce_blocks(wlen4);
+  const int wform = splitk_reduce_form(wsplits);
+  const ReduceDxArgs a{(const float4v *)dpartial, dlen4, dx,
+                       (const ushort8 *)bx, (const ushort8 *)by, mask, mean,
+                       invstd, bn_slab, M, C8, relu};
+  const ReduceDwArgs b{(const float4v *)wpartial, wsplits, wlen4, dw};
+  const int dx_first = mode == 2;
+#define RP_CASE(DS, WS)                                                        \
+  if (dsplits == DS && wform == WS) {                                          \
+    if (stats)                                                                 \
+      reduce_pair_k<true, DS, WS><<<nb_dx + nb_dw, 256, 0, strm>>>(            \
+          a, nb_dx, b, nb_dw, dx_first);                                       \
+    else                                                                       \
+      reduce_pair_k<false, DS, WS><<<nb_dx + nb_dw, 256, 0, strm>>>(           \
+          a, nb_dx, b, nb_dw, dx_first);                                       \
+    g_pair_reduce_count.fetch_add(1, std::memory_order_relaxed);               \
+    return true;                                                               \
+  }
+  REDUCE_PAIR_TABLE(RP_CASE)
+#undef RP_CASE
+  return false;
+}
+
 // conv_wgrad_implicit (bf16 dw) + conv_dgrad of a stride-1 conv
 extern "C" hipError_t conv_dgrad_wgrad(const void *dy, const void *w,
                                        const void *x, void *dx, void *dw,
@@ -851,6 +915,11 @@ extern "C" hipError_t conv_dgrad_wgrad(const void *dy, const void *w,
                             strm);
   if (e != hipSuccess) return e;
   if (dsplits > 1) {
+    if (conv_reduce_pair(false, dpartial, dsplits, dx, (long)N * H * W, C,
+                         nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                         nullptr, wpartial, wsplits, (long)Kout * R * S * C,
+                         dw, strm))
+      return hipGetLastError();
     e = splitk_reduce(dpartial, dsplits, (long)N * H * W * C, dx, 1, strm);
     if (e != hipSuccess) return e;
   }
@@ -881,6 +950,10 @@ extern "C" hipError_t conv_dgrad_bn_wgrad(
                             &dsplits, dpartial, &wsplits, wpartial, mode == 2,
                             strm);
   if (e != hipSuccess) return e;
+  if (conv_reduce_pair(true, dpartial, dsplits, dx, (long)N * H * W, C, bx, by,
+                       mask, mean, invstd, relu, bn_slab, wpartial, wsplits,
+                       (long)Kout * R * S * C, dw, strm))
+    return hipGetLastError();
   e = bn_reduce_stats_bwd_launch(dpartial, dsplits, dx, bx, by, mask, mean,
                                  invstd, relu, bn_slab, (long)N * H * W, C,
                                  strm);

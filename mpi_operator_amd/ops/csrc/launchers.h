@@ -345,6 +345,14 @@ hipError_t conv_wgrad_implicit(const void *dy, const void *x, float *partial,
 // 1: one grid with the wgrad workgroups first, 2: dgrad first; returns the
 // previous mode.
 int conv_set_pair_bwd(int mode);
+// After such a pair, the dx reduce (plain, or with the BN-backward slab) and
+// the dw reduce run as one grid (reduce_pair.h) where both slabs exist and
+// the (dx splits, dw splits) combination is one conv.hip lists; bit for bit
+// the two launches. mode 0: two launches, 1: one grid with the dw blocks
+// first, 2: dx blocks first; returns the previous mode.
+int conv_set_pair_reduce(int mode);
+// pair-reduce launches this process has issued (a host counter)
+long conv_pair_reduce_count();
 hipError_t conv_dgrad_wgrad(const void *dy, const void *w, const void *x,
                             void *dx, void *dw, int N, int H, int W, int C,
                             int Kout, int R, int S, int pad, int HO, int WO,
